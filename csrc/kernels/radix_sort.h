@@ -100,7 +100,8 @@ __device__ __forceinline__ int block_excl_sum256(int x, int* red, int& total) {
 }
 
 // one block per digit: offs[d][t] = sum_{t' < t} cnt[d][t'], tot[d] = sum_t cnt[d][t]
-__global__ __launch_bounds__(256) void radix_digit_scan(const int* __restrict__ cnt, int* __restrict__ offs,
+// (static, like scan_max_excl_kernel: every .hip that includes this header has its own)
+static __global__ __launch_bounds__(256) void radix_digit_scan(const int* __restrict__ cnt, int* __restrict__ offs,
                                                         int* __restrict__ tot, int ntiles) {
   __shared__ int red[4];
   const long row = (long)blockIdx.x * ntiles;
@@ -262,7 +263,7 @@ inline int sort_pairs(unsigned* k0, int* v0, unsigned* k1, int* v1, int n, int n
 // exclusive prefix max of a[0..n) in place from `init`: ONE 1024-thread block
 // walks the array in chunks of 4096 (int4 per thread, coalesced), scanning each
 // chunk through wave shuffles + LDS and carrying the running max between chunks
-__global__ __launch_bounds__(1024) void scan_max_excl_kernel(int* __restrict__ a, int n, int init) {
+static __global__ __launch_bounds__(1024) void scan_max_excl_kernel(int* __restrict__ a, int n, int init) {
   __shared__ int wmax[16];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   int carry = init;

@@ -228,6 +228,7 @@ class WideDeepConfig:
     mlp: Tuple[int, ...] = (1024, 512, 256)
     embed_lr: float = 1e-3
     owners: Optional[int] = None       # PS-owner ranks for the tables (None = every rank)
+    exchange: Optional[str] = None     # world > 1 sender side: "host" | "device" (None = KFA_EMB_EXCHANGE, host)
 
     @classmethod
     def tiny(cls) -> "WideDeepConfig":
@@ -261,7 +262,7 @@ class WideDeep(nn.Module):
             device = torch.device("cuda", torch.cuda.current_device())
         # the tables are created on their final device (22.9 M x 72 fp32 + Adam moments)
         self.tables = ShardedEmbedding(sum(cfg.cardinalities), cfg.row_width, owners=cfg.owners,
-                                       lr=cfg.embed_lr, init_std=0.01, device=device)
+                                       lr=cfg.embed_lr, init_std=0.01, device=device, exchange=cfg.exchange)
         dims = [cfg.dense_pad + nf * cfg.embed_dim, *cfg.mlp]
         self.weights = nn.ParameterList()
         self.biases = nn.ParameterList()
@@ -323,9 +324,10 @@ def wide_deep_loss(model, *batch):
 
 def prepare_batch(model: "WideDeep", dense: torch.Tensor, ids: torch.Tensor, labels: torch.Tensor, device):
     """Host batch -> device batch whose ids carry the embedding exchange's split
-    sizes, computed on the host (``ShardedEmbedding.plan``) before the copy."""
+    sizes, computed on the host (``ShardedEmbedding.plan``) before the copy.  A table
+    whose exchange runs on the device (``exchange="device"``) plans there: no host plan."""
     plan = None
-    if model.tables.world > 1:
+    if model.tables.world > 1 and model.tables.exchange != "device":
         gids = ids.cpu() + model.offsets.cpu().view(1, -1)
         plan = model.tables.plan(gids)
     ids_d = ids.to(device)

@@ -26,7 +26,11 @@ the PS applies the optimizer (``:184, :256``).  MI355X design:
 * with one rank (or CPU) the same code runs without collectives;
 * the split sizes of the two exchanges come from :meth:`ShardedEmbedding.plan`
   on the host copy of the ids (CPU bincount + a gloo all-to-all of the counts)
-  when the batch carries one, so the step never blocks on a device ``.tolist()``.
+  when the batch carries one, so the step never blocks on a device ``.tolist()``;
+* ``exchange="device"`` (opt-in; ``KFA_EMB_EXCHANGE``): the sender's dedup, row expansion
+  and gradient pre-sum run on ``csrc/kernels/sparse_exchange.hip`` instead
+  (``parallel/sparse_exchange.py``) — no host plan, one event wait on 2 world + 2
+  integers per lookup, a pre-sum without atomics (bitwise reproducible).
 
 Parameters marked ``_kfa_sparse`` are skipped by ``split_params`` (they are not
 part of the dense flat groups / all-reduce).
@@ -42,6 +46,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from ..ops import _lib
+from . import sparse_exchange as _xchg
 
 _P, _L, _I, _F = _lib.P, _lib.L, _lib.I, _lib.F
 _lib.register("kfa_scatter_add_rows", [_P, _P, _P, _L, _I, _P])
@@ -81,14 +86,30 @@ def _a2a(out: torch.Tensor, inp: torch.Tensor, out_splits: List[int], in_splits:
         dist.all_to_all_single(out, inp, out_splits, in_splits, group=pg)
 
 
+def _device_exchange(emb: "ShardedEmbedding", ids: torch.Tensor, plan) -> bool:
+    """The lookup's sender side runs on the device-side dedup / expand / pre-sum kernels
+    (``parallel/sparse_exchange.py``): opted in, more than one rank, the table on the GPU,
+    dedup on, contiguous int64 ids, sizes within the kernels' limits and no host plan."""
+    return (emb.exchange == "device" and emb.world > 1 and emb.weight.is_cuda and emb.dedup and plan is None
+            and ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous()
+            and _xchg.supported(ids.numel(), emb.dim, emb.owners, emb.rows_per_owner))
+
+
 class _LookupFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ids, weight, emb: "ShardedEmbedding", plan=None):
         ids = ids.reshape(-1)
         n, D = ids.numel(), emb.dim
         comm = emb.world > 1
-        inv = order = None
-        if comm:
+        inv = order = xp = None
+        if comm and _device_exchange(emb, ids, plan):
+            # dedup on the device (csrc/kernels/sparse_exchange.hip): launches only, then the one
+            # host wait of the lookup - the split sizes, 2 world + 2 integers through pinned memory
+            xp = _xchg.build_plan(ids, emb.world, emb.owners, emb.rows_per_owner, emb.num_rows)
+            send_l, recv_l = xp.split_sizes(emb.comm, emb.pg)
+            local = torch.empty(sum(recv_l), dtype=ids.dtype, device=ids.device)
+            _a2a(local, xp.rows, recv_l, send_l, emb.pg, emb.comm)
+        elif comm:
             # local row of each id on its owner; key = owner-major (owner, local row)
             key = (ids % emb.owners) * emb.rows_per_owner + torch.div(ids, emb.owners, rounding_mode="floor")
             if emb.dedup:   # each distinct id crosses the fabric once per sender, both ways
@@ -126,7 +147,9 @@ class _LookupFn(torch.autograd.Function):
         if comm:
             back = torch.empty(sum(send_l), D, dtype=rows.dtype, device=rows.device)
             _a2a(back, rows, send_l, recv_l, emb.pg, emb.comm)
-            if inv is not None:
+            if xp is not None:
+                out = _xchg.expand_rows(back, xp)
+            elif inv is not None:
                 out = back.index_select(0, inv)
             else:
                 out = torch.empty_like(back)
@@ -134,10 +157,12 @@ class _LookupFn(torch.autograd.Function):
             isz = ids.element_size()
             emb.exchange_bytes = {"lookups": n, "sent_ids": sum(send_l), "ids": sum(send_l) * isz,
                                   "rows": sum(send_l) * D * rows.element_size(),
-                                  "grads": sum(send_l) * D * rows.element_size()}
+                                  "grads": sum(send_l) * D * rows.element_size(),
+                                  "path": "device" if xp is not None else "host"}
         else:
             out = rows
         ctx.emb = emb
+        ctx.xp = xp
         e = torch.empty(0, device=ids.device)
         ctx.save_for_backward(local, order if order is not None else e, inv if inv is not None else e)
         ctx.splits = (send_l, recv_l)
@@ -150,7 +175,10 @@ class _LookupFn(torch.autograd.Function):
         send_l, recv_l = ctx.splits
         dout = dout.contiguous()
         if emb.world > 1:
-            if inv.numel():   # one pre-summed (fp32) gradient per distinct id of this sender
+            if ctx.xp is not None:   # the same pre-sum in one HIP pass pair, fixed order, no fp32 copies
+                d_send = _xchg.presum_rows(dout.to(torch.bfloat16), ctx.xp)
+                ctx.xp = None
+            elif inv.numel():   # one pre-summed (fp32) gradient per distinct id of this sender
                 gu = torch.zeros(sum(send_l), emb.dim, dtype=torch.float32, device=dout.device)
                 gu.index_add_(0, inv, dout.float())
                 d_send = gu.to(dout.dtype)
@@ -170,8 +198,13 @@ class ShardedEmbedding(nn.Module):
     def __init__(self, num_rows: int, dim: int, owners: Optional[int] = None, process_group=None,
                  optimizer: str = "adam", lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 0.0, init_std: float = 0.01, seed: int = 0,
-                 device=None):
+                 device=None, exchange: Optional[str] = None):
         super().__init__()
+        # sender side of a world > 1 lookup: "host" (torch.unique plan, index_select, index_add_)
+        # or "device" (csrc/kernels/sparse_exchange.hip); KFA_EMB_EXCHANGE sets the default
+        self.exchange = (exchange or os.environ.get("KFA_EMB_EXCHANGE") or "host").lower()
+        if self.exchange not in ("host", "device"):
+            raise ValueError(f"ShardedEmbedding: exchange must be 'host' or 'device', got {self.exchange!r}")
         self.pg = process_group
         self.comm = None  # the job's communicator (parallel/comm.py), attached by the Engine
         init = dist.is_initialized()
