@@ -96,3 +96,15 @@ __device__ __forceinline__ uint32_t drop_hash(uint64_t seed, uint64_t i) {
 static inline int kfa_status() { return (int)hipGetLastError(); }
 
 static inline int kfa_ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// compute units of the current device, cached per process; 256 (MI355X) when the query fails
+inline int kfa_cu_count() {
+  static int cached = 0;
+  if (!cached) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cached, hipDeviceAttributeMultiprocessorCount, dev);
+    if (cached <= 0) cached = 256;
+  }
+  return cached;
+}

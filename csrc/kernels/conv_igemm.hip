@@ -29,8 +29,10 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "tile.h"
 
 namespace {
+using namespace tile;
 
 #ifndef KFA_CONV_STORE_AUX
 #define KFA_CONV_STORE_AUX 2  // output stores non-temporal (streamed; +1.7 % ResNet-50 vs 0, docs/kernels.md)
@@ -76,64 +78,12 @@ struct Geo {
   unsigned t_bytes, b_bytes, d_bytes;  // buffer extents: out-of-range lanes read 0 / drop stores
 };
 
-// Buffer-resource loads/stores (T8): the hardware range check turns padding
-// taps and tile tails into zero loads / dropped stores with NO branch, so hipcc
-// can keep counted vmcnt waits instead of draining to vmcnt(0) around each
-// guarded load (cdna_hip_programming.md §5 'Three .s-level traps' (c)).
-constexpr unsigned kOOB = 0x80000000u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
 #ifndef KFA_CONV_EPI_LOAD_AUX
 #define KFA_CONV_EPI_LOAD_AUX 2  // epilogue addend / BN-input loads non-temporal (read once; +0.2 %)
 #endif
-__device__ __forceinline__ uint4 bload16(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  auto v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, KFA_CONV_EPI_LOAD_AUX);
-  return *reinterpret_cast<uint4*>(&v);
-}
-
-// 16 B per lane buffer -> LDS DMA (buffer_load_dwordx4 ... lds): voff per lane,
-// soff wave-uniform.  A plain device function: the builtin named directly inside
-// the templated kernel's lambdas stops clang's host pass from emitting the
-// kernels' launch stubs.
-__device__ __forceinline__ void buf_dma16(__amdgpu_buffer_rsrc_t r, bf16_t* lds, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
 #ifndef KFA_CONV_LOAD_AUX
-#define KFA_CONV_LOAD_AUX 0
+#define KFA_CONV_LOAD_AUX 0  // cache policy of the gathered activation operand's DMA (each element used by one tile column only)
 #endif
-// the gathered activation operand (each element used by one tile column only)
-__device__ __forceinline__ void buf_dma16_act(__amdgpu_buffer_rsrc_t r, bf16_t* lds, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0,
-                                           KFA_CONV_LOAD_AUX);
-}
-
-// x / d for 0 <= x < 2^24 via an fp32 reciprocal + one correction step
-// (hipcc's int32 division is a ~40-instruction sequence; these run per row).
-__device__ __forceinline__ int fdiv(int x, int d, float rcp) {
-  int q = (int)((float)x * rcp);
-  const int r = x - q * d;
-  q += (r >= d) - (r < 0);
-  return q;
-}
-
-// Workgroup barrier for LDS hand-off only.  __syncthreads() is a workgroup
-// release fence too, which makes hipcc drain vmcnt(0) for the epilogue's
-// global stores — and with them the prefetch loads in flight.  Nothing in this
-// kernel needs global-memory ordering between waves, only LDS.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void lgkm_wait() {
-  if constexpr (N == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-  else static_assert(N < 0, "lgkm_wait: add the literal");
-}
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * BK + ((chunk ^ ((row >> 1) & 7)) << 3); }
 
 // WM x WN waves, each owning TM x TN MFMA 16x16 tiles (wave tile 16TM x 16TN)
 // (8 waves: 256 x 256 tiles of 128 x 64 per wave, one block per CU — half the
@@ -213,19 +163,19 @@ __device__ __forceinline__ void conv_epilogue(const Geo& g, floatx4 (&acc)[TN][T
     if (kE && E)
 #pragma unroll
       for (int it = 0; it < IT; it++) {
-        ev[it] = bload16(er.e, offs[it]);
+        ev[it] = bload16<KFA_CONV_EPI_LOAD_AUX>(er.e, offs[it]);
         if (kEM && bnb.emb) ebits[it] = offs[it] != kOOB ? (unsigned)bnb.emb[offs[it] >> 4] : 0u;
       }
     if (bstat)
 #pragma unroll
       for (int it = 0; it < IT; it++) {
-        bx[it] = bload16(er.bx, offs[it]);
-        if (ymask) by[it] = bload16(er.by, offs[it]);
+        bx[it] = bload16<KFA_CONV_EPI_LOAD_AUX>(er.bx, offs[it]);
+        if (ymask) by[it] = bload16<KFA_CONV_EPI_LOAD_AUX>(er.by, offs[it]);
         if (bmask) mbits[it] = offs[it] != kOOB ? (unsigned)bnb.mb[offs[it] >> 4] : 0u;  // 8 bf16 = 16 B per bit byte
       }
 
     if (hh == 0 && first_barrier) lds_barrier();  // every wave is done reading the operand buffer under `stage`
-    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave read back its previous pass
+    else lgkm_wait<0>();  // this wave read back its previous pass
 #pragma unroll
     for (int mj = 0; mj < TMH; mj++)
 #pragma unroll
@@ -235,7 +185,7 @@ __device__ __forceinline__ void conv_epilogue(const Geo& g, floatx4 (&acc)[TN][T
         const uint2 o = make_uint2(pack2(acc[ni][mi][0], acc[ni][mi][1]), pack2(acc[ni][mi][2], acc[ni][mi][3]));
         *reinterpret_cast<uint2*>(stage + row * RB + (((col >> 3) ^ (row & (CPR - 1))) << 4) + (col & 7) * 2) = o;
       }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm_wait<0>();
 #pragma unroll
     for (int it = 0; it < IT; it++) {
       const int r = it * (64 / CPR) + lane / CPR;
@@ -364,7 +314,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const bf16_
 #pragma unroll
     for (int i = 0; i < AR; i++) {
       const int m = m0 + rbase + RPP * i;
-      const int cs = (kc ^ ((((i * RPP) + rbase) >> 1) & 7)) * 8;  // this lane's swizzled source chunk
+      const int cs = (kc ^ swz_chunk(i * RPP + rbase)) * 8;  // this lane's swizzled source chunk
       if (m < g.M && lin_a) {
         a_hb[i] = 0;
         a_wb[i] = 0;
@@ -384,12 +334,12 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const bf16_
 #pragma unroll
     for (int i = 0; i < BR; i++) {
       const int n = n0 + rbase + RPP * i;
-      const int cs = (kc ^ ((((i * RPP) + rbase) >> 1) & 7)) * 8;
+      const int cs = (kc ^ swz_chunk(i * RPP + rbase)) * 8;
       b_off[i] = n < g.N ? (unsigned)(n * g.K + cs) * 2u : kOOB;
     }
   };
 
-  // Operand staging: LDS-DMA (global_load_lds_dwordx4).  Each wave-instruction
+  // Operand staging: LDS-DMA (buf_dma16, tile.h).  Each wave-instruction
   // writes 1 KiB = 8 tile rows lane-linearly; the XOR swizzle is applied on the
   // per-lane SOURCE address (rule 21); padding taps / tails read as zero (range check).
   // No staging VGPRs, no ds_write pass; waits are counted by hand.
@@ -451,14 +401,14 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const bf16_
     } else if (lin_a) {  // the whole offset but the slice's is fixed per tile (a_vo, setup)
 #pragma unroll
       for (int i = 0; i < AR; i++)
-        buf_dma16_act(rT, As + buf * BM * BK + (i * RPP + wave * 8) * BK, a_vo[i], k0 * 2);
+        buf_dma16<KFA_CONV_LOAD_AUX>(rT, As + buf * BM * BK + (i * RPP + wave * 8) * BK, a_vo[i], k0 * 2);
     } else {
 #pragma unroll
       for (int i = 0; i < AR; i++) {
         const int ih = a_hb[i] + dh, iw = a_wb[i] + dw;
         const bool ok = (unsigned)ih < (unsigned)g.H && (unsigned)iw < (unsigned)g.W;
         const int vo = ok ? a_vo[i] + ta_off : (int)kOOB;  // selects, no branch
-        buf_dma16_act(rT, As + buf * BM * BK + (i * RPP + wave * 8) * BK, vo, c0 * 2);
+        buf_dma16<KFA_CONV_LOAD_AUX>(rT, As + buf * BM * BK + (i * RPP + wave * 8) * BK, vo, c0 * 2);
       }
     }
 #pragma unroll
@@ -500,17 +450,17 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const bf16_
     };
     if constexpr (TM + 2 * TN <= 15) {
 #pragma unroll
-      for (int i = 0; i < TN; i++) bf[0][i] = rd(Bb + swz(wn * TN * 16 + i * 16 + fr, fq));
+      for (int i = 0; i < TN; i++) bf[0][i] = rd(Bb + swz128(wn * TN * 16 + i * 16 + fr, fq));
 #pragma unroll
-      for (int i = 0; i < TM; i++) af[0][i] = rd(Ab + swz(wm * TM * 16 + i * 16 + fr, fq));
+      for (int i = 0; i < TM; i++) af[0][i] = rd(Ab + swz128(wm * TM * 16 + i * 16 + fr, fq));
 #pragma unroll
-      for (int i = 0; i < TN; i++) bf[1][i] = rd(Bb + swz(wn * TN * 16 + i * 16 + fr, 4 + fq));
+      for (int i = 0; i < TN; i++) bf[1][i] = rd(Bb + swz128(wn * TN * 16 + i * 16 + fr, 4 + fq));
       lgkm_wait<TN>();  // k-half 0's fragments landed; k-half 1's B reads may still be in flight
       __builtin_amdgcn_sched_barrier(0);
       mfma(0);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int i = 0; i < TM; i++) af[1][i] = rd(Ab + swz(wm * TM * 16 + i * 16 + fr, 4 + fq));
+      for (int i = 0; i < TM; i++) af[1][i] = rd(Ab + swz128(wm * TM * 16 + i * 16 + fr, 4 + fq));
       lgkm_wait<0>();
       __builtin_amdgcn_sched_barrier(0);
       mfma(1);
@@ -523,9 +473,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const bf16_
 #pragma unroll
       for (int ks = 0; ks < 2; ks++) {
 #pragma unroll
-        for (int i = 0; i < TM; i++) af[ks][i] = rd(Ab + swz(wm * TM * 16 + i * 16 + fr, ks * 4 + fq));
+        for (int i = 0; i < TM; i++) af[ks][i] = rd(Ab + swz128(wm * TM * 16 + i * 16 + fr, ks * 4 + fq));
 #pragma unroll
-        for (int i = 0; i < TN; i++) bf[ks][i] = rd(Bb + swz(wn * TN * 16 + i * 16 + fr, ks * 4 + fq));
+        for (int i = 0; i < TN; i++) bf[ks][i] = rd(Bb + swz128(wn * TN * 16 + i * 16 + fr, ks * 4 + fq));
         lgkm_wait<0>();
         __builtin_amdgcn_sched_barrier(0);
         mfma(ks);
@@ -536,10 +486,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const bf16_
       for (int ks = 0; ks < 2; ks++) {
 #pragma unroll
         for (int i = 0; i < TM; i++)
-          af[ks][i] = *reinterpret_cast<const short8*>(Ab + swz(wm * TM * 16 + i * 16 + fr, ks * 4 + fq));
+          af[ks][i] = *reinterpret_cast<const short8*>(Ab + swz128(wm * TM * 16 + i * 16 + fr, ks * 4 + fq));
 #pragma unroll
         for (int i = 0; i < TN; i++)
-          bf[ks][i] = *reinterpret_cast<const short8*>(Bb + swz(wn * TN * 16 + i * 16 + fr, ks * 4 + fq));
+          bf[ks][i] = *reinterpret_cast<const short8*>(Bb + swz128(wn * TN * 16 + i * 16 + fr, ks * 4 + fq));
         mfma(ks);
       }
     }
@@ -609,9 +559,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const bf16_
     }
   };
   auto pro_wait = [&]() {  // this slice's A loads retired (its BR B-operand DMAs may still be in flight)
-    if constexpr (BR == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (BR == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<(BR == 4 || BR == 2) ? BR : 0>();
   };
 
   if (nk == 0) {  // no taps reach these outputs (strided dgrad parity class): D = 0 (+ E)
@@ -630,7 +578,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const bf16_
     if (total > 0) {
       pro_wait();
       pro_store(0);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the loop's first barrier publishes them
+      lgkm_wait<0>();  // the loop's first barrier publishes them
     }
   }
   for (int st = 0; st < total; st++) {
@@ -692,17 +640,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const bf16_
 template <int WR>
 __device__ __forceinline__ void pp_vm_wait(int n) {  // s_waitcnt vmcnt(n), n in [0, 2*WR + 8/WR]
   switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
+    KFA_VMW(0) KFA_VMW(1) KFA_VMW(2) KFA_VMW(3) KFA_VMW(4) KFA_VMW(5) KFA_VMW(6) KFA_VMW(7) KFA_VMW(8) KFA_VMW(9)
+    default: vm_wait<10>(); break;
   }
 }
 
@@ -741,7 +680,7 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(const bf16_t* __restric
   // A piece h, instruction j: wave-row j's rows h*64 + [0, 64);  B piece h,
   // instruction j: wave-columns 2j, 2j+1's columns h*32 + [0, 32).
   const int prow = wave * 8 + (lane >> 3);
-  const int lc = (lane & 7) ^ ((prow >> 1) & 7);
+  const int lc = (lane & 7) ^ swz_chunk(prow);
   int a_hb[2][WR], a_wb[2][WR], a_vo[2][WR];  // [h: A0 / A1][j]
   int b_vo[2][WC / 2];                        // [h: B0 / B1][j]
 #pragma unroll
@@ -802,13 +741,13 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(const bf16_t* __restric
             const bool ok = (unsigned)ih < (unsigned)g.H && (unsigned)iw < (unsigned)g.W;
             vo = ok ? vo + ta_off : (int)kOOB;
           }
-          buf_dma16_act(rT, reinterpret_cast<bf16_t*>(dst + j * 64 * 128), vo, ta_soff);
+          buf_dma16<KFA_CONV_LOAD_AUX>(rT, dst + j * 64 * 128, vo, ta_soff);
         }
       } else {
         constexpr int h = p == 2;
 #pragma unroll
         for (int j = 0; j < WC / 2; j++)
-          buf_dma16(rB, reinterpret_cast<bf16_t*>(dst + j * 64 * 128), b_vo[h][j], kt * BK * 2);
+          buf_dma16(rB, dst + j * 64 * 128, b_vo[h][j], kt * BK * 2);
       }
     }
   };
@@ -1160,17 +1099,7 @@ KFA_API int kfa_conv_igemm(const bf16_t* T, const bf16_t* B, bf16_t* D, const bf
   g.b_bytes = (unsigned)bb;
   g.d_bytes = (unsigned)db;
   if (g.M <= 0) return 0;
-  int cus = 256;
-  {
-    static int cached = 0;
-    if (!cached) {
-      int dev = 0;
-      hipGetDevice(&dev);
-      hipDeviceGetAttribute(&cached, hipDeviceAttributeMultiprocessorCount, dev);
-      if (cached <= 0) cached = 256;
-    }
-    cus = cached;
-  }
+  const int cus = kfa_cu_count();
   // persistent grid: 2 resident blocks per CU (64 KB LDS, <=256 VGPR/2 waves).
   // KFA_CONV_OVERSUB=k caps the grid at k x that (0: one block per tile), so the
   // dispatcher, not the tile ranges, balances the work when other kernels (RCCL)
@@ -1226,13 +1155,7 @@ KFA_API int kfa_conv_igemm_bnpro(const bf16_t* T, const bf16_t* B, bf16_t* D, co
   g.b_bytes = (unsigned)bb;
   g.d_bytes = (unsigned)db;
   if (g.M <= 0) return 0;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
+  const int cus = kfa_cu_count();
   const Pro pro{ss, y};
   const unsigned epi = stats ? kEpiStats : 0u;
   const int tab = 8 * C;  // the [scale | shift] table behind the operand ring

@@ -17,7 +17,7 @@
 // CDNA4 tiling (cdna_hip_programming.md §5): 512 threads = 8 waves, block tile
 // 256 x BN (BN = 256: 2x4 waves of 128x64; BN = 128: 4x2 waves of 64x64),
 // v_mfma_f32_16x16x32_bf16, K advances 32 per LDS slot.  Operands move
-// HBM/L2 -> LDS by LDS-DMA (global_load_lds, 16 B per lane) into a 4-slot
+// HBM/L2 -> LDS by LDS-DMA (tile.h, 16 B per lane) into a 4-slot
 // ring: k-step t+3 is issued while t is multiplied, ONE raw s_barrier per
 // k-step, and the counted vmcnt in front of it keeps the two younger k-steps
 // in flight (never vmcnt(0) in the main loop — "Pipelining across barriers").
@@ -28,26 +28,13 @@
 // row-panel (T1, bijective remap).  Each wave stages its tile through LDS so
 // the write-out is 16 B per lane, 8 rows x 128 B per wave instruction.
 #include "common.h"
-
-#include <utility>
+#include "tile.h"
 
 namespace {
-
-// Compile-time loop: f(std::integral_constant<int, 0>) ... f(<N-1>) — keeps
-// register-array indices constant where `#pragma unroll` is not honoured
-// (a runtime index sends the whole accumulator array to scratch, rule 20).
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
+using namespace tile;
 
 constexpr int GK = 32;     // k per ring slot (one MFMA k-step)
 constexpr int NSLOT = 4;   // ring depth: prefetch distance NSLOT - 1
-constexpr unsigned kOOB = 0x80000000u;
 
 enum Act { kNone = 0, kGelu = 1, kTanh = 2, kRelu = 3 };
 
@@ -85,43 +72,6 @@ struct GemmArgs {
   int M, N, K, lda, ldb, ldc, act, dact;
   unsigned c_bytes;    // extent of C / E / Z / Zin
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ uint4 bload(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  auto v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-  return *reinterpret_cast<uint4*>(&v);
-}
-// aux: cache policy (2 = non-temporal: streamed past the caches)
-__device__ __forceinline__ void bstore(__amdgpu_buffer_rsrc_t r, unsigned off, uint4 v, int aux = 0) {
-  using V = decltype(__builtin_amdgcn_raw_buffer_load_b128(r, 0, 0, 0));
-  if (aux == 2) __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<V*>(&v), r, off, 0, 2);
-  else __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<V*>(&v), r, off, 0, 0);
-}
-
-// 16 B per lane HBM/L2 -> LDS.  A plain device function: the builtin named
-// directly inside the templated kernel's lambda stops clang's host pass from
-// emitting the kernel's launch stub.
-__device__ __forceinline__ void lds_dma16(const bf16_t* src, bf16_t* dst) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-
-// 16 B per lane buffer -> LDS DMA (buffer_load_dwordx4 ... lds), soff wave-uniform
-__device__ __forceinline__ void pp_dma(__amdgpu_buffer_rsrc_t r, char* lds, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-  else static_assert(N < 0, "vm_wait: add the literal");
-}
 
 // k-step t+1 landed for this wave; `ahead` younger k-steps (0..2) may stay in flight
 template <int GL>
@@ -222,23 +172,23 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& g, floatx4 (&acc)[
     unpack8(*reinterpret_cast<const uint4*>(stage + r * RB + ((c ^ (r & 7)) << 4)), f);
     if (g.E) {
       float h[8];
-      unpack8(bload(rE, off), h);
+      unpack8(bload16(rE, off), h);
 #pragma unroll
       for (int j = 0; j < 8; j++) f[j] += h[j];
     }
-    if (g.Z) bstore(rZ, off, pack8(f), NTST ? 2 : 0);
+    if (g.Z) bstore16<NTST ? 2 : 0>(rZ, off, pack8(f));
     if (g.act) {
 #pragma unroll
       for (int j = 0; j < 8; j++) f[j] = act_fwd(f[j], g.act);
     }
     if (g.Zin) {
       float z[8];
-      unpack8(bload(rZi, off), z);
+      unpack8(bload16(rZi, off), z);
 #pragma unroll
       for (int j = 0; j < 8; j++) f[j] *= act_bwd(z[j], g.dact);
     }
     const uint4 o = pack8(f);
-    bstore(rC, off, o, NTST ? 2 : 0);
+    bstore16<NTST ? 2 : 0>(rC, off, o);
     if (g.dbias && off != kOOB) {
       float q[8];
       unpack8(o, q);  // the bf16-rounded values the next layer sees
@@ -279,18 +229,9 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void gemm_nt_kernel(GemmArgs g, co
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: LDS-DMA bases in SGPRs
   const int wm = wave % WM, wn = wave / WM;
-  // T1: blocks that share an XCD (blockIdx % 8) take consecutive tiles (bijective remap)
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, x8 = bid & 7;
-  const int wg = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (bid >> 3);
-  // Grouped raster: consecutive tiles walk GM row-panels column-major, so the
-  // ~32 tiles an XCD runs at once form a GM x (32/GM) block whose A and B
-  // panels fit its 4 MB L2 together (row-major order would stream all of B
-  // past every A panel).
-  const int ntn = (g.N + BN - 1) / BN, ntm = (g.M + BM - 1) / BM;
-  constexpr int GM = 4;
-  const int grp = wg / (GM * ntn), gm0 = grp * GM, gmn = min(GM, ntm - gm0), rem = wg - grp * GM * ntn;
-  const int m0 = (gm0 + rem % gmn) * BM, n0 = (rem / gmn) * BN;
+  // tile order: XCD remap + grouped raster, 4 row-panels high (tile.h)
+  const int2 tl = raster_tile(xcd_remap(blockIdx.x, gridDim.x), (g.M + BM - 1) / BM, (g.N + BN - 1) / BN, 4);
+  const int m0 = tl.x * BM, n0 = tl.y * BN;
 
   // LDS-DMA plan: instruction i of wave w fills rows (w*G + i)*16 + lane/4, physical
   // chunk lane&3, from logical chunk (lane&3) ^ swz(row), swz(row) = (row >> 2) & 2
@@ -315,12 +256,10 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void gemm_nt_kernel(GemmArgs g, co
     const bool kin = k0 + lch * 8 < g.K;  // K tail (K % 8 == 0): chunks past K read as 0
 #pragma unroll
     for (int i = 0; i < GA; i++)
-      pp_dma(rA, reinterpret_cast<char*>(As + slot * A_SLOT + (wave * GA + i) * 16 * GK), kin ? a_vo[i] : (int)kOOB,
-             k0 * 2);
+      buf_dma16(rA, As + slot * A_SLOT + (wave * GA + i) * 16 * GK, kin ? a_vo[i] : (int)kOOB, k0 * 2);
 #pragma unroll
     for (int i = 0; i < GB; i++)
-      pp_dma(rB, reinterpret_cast<char*>(Bs + slot * B_SLOT + (wave * GB + i) * 16 * GK), kin ? b_vo[i] : (int)kOOB,
-             k0 * 2);
+      buf_dma16(rB, Bs + slot * B_SLOT + (wave * GB + i) * 16 * GK, kin ? b_vo[i] : (int)kOOB, k0 * 2);
   };
 
   // this lane's 16-B operand piece of a 16-row tile: row fr, logical chunk fq
@@ -357,7 +296,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void gemm_nt_kernel(GemmArgs g, co
         acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[ni], af[mi], acc[ni][mi], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
     ring_wait<GL>((t + NS - 1 < nk ? t + NS - 1 : nk - 1) - (t + 1));
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
   }
 
   // ---- epilogue: acc[ni][mi][r] = C(m = m0 + wm*16TM + 16mi + fr, n = n0 + wn*64 + 16ni + 4fq + r)
@@ -408,12 +347,10 @@ __global__ __launch_bounds__(512) void gemm_pt_kernel(GemmArgs g, const bf16_t* 
   const int nslot = (nwg - xcd + G8 - 1) / G8;
   const int t_lo = (int)((long)ntiles * xcd / G8), t_hi = (int)((long)ntiles * (xcd + 1) / G8);
   const int my_tiles = t_hi - t_lo > slot ? (t_hi - t_lo - slot + nslot - 1) / nslot : 0;
-  constexpr int GM = 4;
   auto tile_mn = [&](int i, int& m0, int& n0) __attribute__((always_inline)) {
-    const int wg = t_lo + slot + i * nslot;
-    const int grp = wg / (GM * ntn), gm0 = grp * GM, gmn = min(GM, ntm - gm0), rem = wg - grp * GM * ntn;
-    m0 = (gm0 + rem % gmn) * BM;
-    n0 = (rem / gmn) * BN;
+    const int2 tl = raster_tile(t_lo + slot + i * nslot, ntm, ntn, 4);
+    m0 = tl.x * BM;
+    n0 = tl.y * BN;
   };
 
   const int lrow = lane >> 2, lch = (lane & 3) ^ ((lane >> 4) & 2);
@@ -501,23 +438,23 @@ __global__ __launch_bounds__(512) void gemm_pt_kernel(GemmArgs g, const bf16_t* 
         unpack8(v[it], f);
         if (g.E) {
           float h[8];
-          unpack8(bload(rE, off), h);
+          unpack8(bload16(rE, off), h);
 #pragma unroll
           for (int j = 0; j < 8; j++) f[j] += h[j];
         }
-        if (g.Z) bstore(rZ, off, pack8(f));
+        if (g.Z) bstore16(rZ, off, pack8(f));
         if (g.act) {
 #pragma unroll
           for (int j = 0; j < 8; j++) f[j] = act_fwd(f[j], g.act);
         }
         if (g.Zin) {
           float z[8];
-          unpack8(bload(rZi, off), z);
+          unpack8(bload16(rZi, off), z);
 #pragma unroll
           for (int j = 0; j < 8; j++) f[j] *= act_bwd(z[j], g.dact);
         }
         const uint4 o = pack8(f);
-        bstore(rC, off, o);
+        bstore16(rC, off, o);
         if (g.dbias && off != kOOB) {
           float q[8];
           unpack8(o, q);
@@ -575,21 +512,8 @@ __global__ __launch_bounds__(512) void gemm_pt_kernel(GemmArgs g, const bf16_t* 
         const int ei = s - e;
         if (ei >= 0 && ei % nk == nk - 1) eps++;
       }
-      const int nwait = GL * steps + XS * eps;
-      switch (nwait) {
-#define KFA_VMW(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-        KFA_VMW(0) KFA_VMW(1) KFA_VMW(2) KFA_VMW(3) KFA_VMW(4) KFA_VMW(5) KFA_VMW(6) KFA_VMW(7)
-        KFA_VMW(8) KFA_VMW(9) KFA_VMW(10) KFA_VMW(11) KFA_VMW(12) KFA_VMW(13) KFA_VMW(14) KFA_VMW(15)
-        KFA_VMW(16) KFA_VMW(17) KFA_VMW(18) KFA_VMW(19) KFA_VMW(20) KFA_VMW(21) KFA_VMW(22) KFA_VMW(23)
-        KFA_VMW(24) KFA_VMW(25) KFA_VMW(26) KFA_VMW(27) KFA_VMW(28) KFA_VMW(29) KFA_VMW(30) KFA_VMW(31)
-        KFA_VMW(32) KFA_VMW(33) KFA_VMW(34) KFA_VMW(35) KFA_VMW(36) KFA_VMW(37) KFA_VMW(38) KFA_VMW(39)
-        KFA_VMW(40) KFA_VMW(41) KFA_VMW(42) KFA_VMW(43) KFA_VMW(44) KFA_VMW(45) KFA_VMW(46) KFA_VMW(47)
-        KFA_VMW(48) KFA_VMW(49) KFA_VMW(50) KFA_VMW(51) KFA_VMW(52) KFA_VMW(53) KFA_VMW(54) KFA_VMW(55)
-        KFA_VMW(56) KFA_VMW(57) KFA_VMW(58) KFA_VMW(59) KFA_VMW(60) KFA_VMW(61) KFA_VMW(62)
-#undef KFA_VMW
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      KFA_VM_WAIT_RT(GL * steps + XS * eps)
+      lds_barrier();
     }
   }
 }
@@ -632,24 +556,6 @@ __global__ __launch_bounds__(512) void gemm_pt_kernel(GemmArgs g, const bf16_t* 
 constexpr int PP_BK = 64;
 constexpr int PP_PIECE = 128 * PP_BK * 2;  // bytes per piece
 
-
-template <int N>
-__device__ __forceinline__ void pp_vmcnt() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-}
-// retire every DMA except the pieces issued in the `younger` (0..4) most recent phases
-__device__ __forceinline__ void pp_retire(int younger) {
-  if (younger >= 4) pp_vmcnt<8>();
-  else if (younger == 3) pp_vmcnt<6>();
-  else if (younger == 2) pp_vmcnt<4>();
-  else if (younger == 1) pp_vmcnt<2>();
-  else pp_vmcnt<0>();
-}
-
 template <bool PROBE_NO_EPI = false, bool NTST = false>
 __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs g) {
   constexpr int TM = 8, TN = 4;
@@ -657,21 +563,16 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs g) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  // T1 XCD remap + grouped raster (as gemm_nt_kernel)
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, x8 = bid & 7;
-  const int wg = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (bid >> 3);
-  const int ntn = (g.N + 255) / 256, ntm = (g.M + 255) / 256;
-  constexpr int GM = 4;
-  const int grp = wg / (GM * ntn), gm0 = grp * GM, gmn = min(GM, ntm - gm0), rem = wg - grp * GM * ntn;
-  const int m0 = (gm0 + rem % gmn) * 256, n0 = (rem / gmn) * 256;
+  // tile order as gemm_nt_kernel
+  const int2 tl = raster_tile(xcd_remap(blockIdx.x, gridDim.x), (g.M + 255) / 256, (g.N + 255) / 256, 4);
+  const int m0 = tl.x * 256, n0 = tl.y * 256;
 
   const __amdgpu_buffer_rsrc_t rA = rsrc(g.A, (unsigned)(((long)(g.M - 1) * g.lda + g.K) * 2));
   const __amdgpu_buffer_rsrc_t rB = rsrc(g.B, (unsigned)(((long)(g.N - 1) * g.ldb + g.K) * 2));
   // DMA plan: instruction j of wave w fills piece rows j*64 + w*8 + lane/8,
   // physical chunk lane&7 <- logical chunk (lane&7) ^ ((row >> 1) & 7)
   const int prow = wave * 8 + (lane >> 3);
-  const int lc = (lane & 7) ^ ((prow >> 1) & 7);
+  const int lc = (lane & 7) ^ swz_chunk(prow);
   int voff[4][2];
 #pragma unroll
   for (int j = 0; j < 2; j++) {
@@ -693,16 +594,16 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs g) {
     if (decltype(steady)::value || kt < nk) {
       char* dst = smem + (kt & 1) * (4 * PP_PIECE) + p * PP_PIECE + wave * 8 * 128;
       const __amdgpu_buffer_rsrc_t r = (p == 0 || p == 3) ? rA : rB;
-      pp_dma(r, dst, voff[p][0], kt * PP_BK * 2);
-      pp_dma(r, dst + 64 * 128, voff[p][1], kt * PP_BK * 2);
+      buf_dma16(r, dst, voff[p][0], kt * PP_BK * 2);
+      buf_dma16(r, dst + 64 * 128, voff[p][1], kt * PP_BK * 2);
     }
   };
   auto retire = [&](int P, auto steady) __attribute__((always_inline)) {
     if constexpr (decltype(steady)::value) {
-      pp_vmcnt<8>();
+      vm_wait<8>();
     } else {
       const int younger = min(P, plast) - (P - 3) + 1;
-      pp_retire(younger < 0 ? 0 : younger);
+      tile::retire(younger < 0 ? 0 : younger);
     }
   };
 
@@ -843,22 +744,11 @@ static const bf16_t* gemm_zero_page() {
   return z;
 }
 
-static int gemm_cus() {
-  static int c = 0;
-  if (!c) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-    if (c <= 0) c = 256;
-  }
-  return c;
-}
-
 // Tile width for an M x N output: whole waves of tiles over the CUs, a 256x128
 // tile costing ~0.55 of a 256x256 one (lower arithmetic intensity).
 KFA_API int kfa_gemm_pick_bn(int M, int N) {
   const long tm = (M + 255) / 256;
-  const long cus = gemm_cus();
+  const long cus = kfa_cu_count();
   const long w256 = (tm * ((N + 255) / 256) + cus - 1) / cus;
   const long w128 = (tm * ((N + 127) / 128) + cus - 1) / cus;
   return (N <= 128 || 0.55 * (double)w128 < (double)w256) ? 128 : 256;
@@ -909,7 +799,7 @@ KFA_API int kfa_gemm_nt(const bf16_t* A, const bf16_t* B, bf16_t* C, const bf16_
   if (!dbias || !prow) dpart = nullptr;
   const GemmArgs g{A, B, C, E, bias, Z, Zin, dbias, dpart, M, N, K, lda, ldb, ldc, act, dact, (unsigned)cb};
   if (persistent == 1) {
-    const long cus = gemm_cus();
+    const long cus = kfa_cu_count();
     const int grid = (int)(tiles < cus ? tiles : cus);
     if (bn == 256)
       hipLaunchKernelGGL((gemm_pt_kernel<256>), dim3(grid), dim3(512), 0, st, g, gemm_zero_page());

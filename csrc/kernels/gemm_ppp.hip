@@ -38,55 +38,13 @@
 // depends on it.  Steady k-tiles away from a tile boundary use the fixed
 // vmcnt(8); the boundary k-tiles and the pipeline tail take the runtime count.
 #include "common.h"
-
-#include <utility>
+#include "tile.h"
 
 namespace {
+using namespace tile;
 
 constexpr int BK = 64;
 constexpr int PIECE = 128 * BK * 2;  // bytes per LDS piece (128 rows x 64 k)
-constexpr unsigned kOOB = 0x80000000u;
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(2))) float floatx2_t;
-
-// two floats -> packed bf16x2 (v_cvt_pk_bf16_f32: round to nearest even, NaN kept)
-__device__ __forceinline__ unsigned cvt2(float lo, float hi) {
-  const floatx2_t f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* lds, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
-
-__device__ __forceinline__ void store16(__amdgpu_buffer_rsrc_t r, unsigned off, uint4 v) {
-  using V = decltype(__builtin_amdgcn_raw_buffer_load_b128(r, 0, 0, 0));
-  __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<V*>(&v), r, off, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform runtime n (even, 0..62)
-__device__ __forceinline__ void vm_wait_rt(int n) {
-  switch (n) {
-#define KFA_VMW(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    KFA_VMW(0) KFA_VMW(2) KFA_VMW(4) KFA_VMW(6) KFA_VMW(8) KFA_VMW(10) KFA_VMW(12) KFA_VMW(14)
-    KFA_VMW(16) KFA_VMW(18) KFA_VMW(20) KFA_VMW(22) KFA_VMW(24) KFA_VMW(26) KFA_VMW(28) KFA_VMW(30)
-    KFA_VMW(32) KFA_VMW(34) KFA_VMW(36) KFA_VMW(38) KFA_VMW(40) KFA_VMW(42) KFA_VMW(44) KFA_VMW(46)
-    KFA_VMW(48) KFA_VMW(50) KFA_VMW(52) KFA_VMW(54) KFA_VMW(56) KFA_VMW(58) KFA_VMW(60) KFA_VMW(62)
-#undef KFA_VMW
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
 
 struct PppArgs {
   const bf16_t* A;
@@ -171,9 +129,7 @@ __global__ __launch_bounds__(512, 1) void gemm_ppp_kernel(PppArgs g) {
   const int wr = wave >> 2, wc = wave & 3;
   // T1: blocks that share an XCD (blockIdx % 8) get consecutive logical indices,
   // so the tiles an XCD runs at one time are neighbours in the grouped raster
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, x8 = bid & 7;
-  const int lc = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (bid >> 3);
+  const int nwg = gridDim.x, lc = xcd_remap(blockIdx.x, nwg);
   ppp_stagger(g.stagger, lc);
   const int ntn = (g.N + BN - 1) / BN, ntm = (g.M + 255) / 256, ntiles = ntm * ntn;
   const int nk = (g.K + BK - 1) / BK;  // K % 8 == 0; a partial last k-tile reads zeros past K
@@ -189,9 +145,9 @@ __global__ __launch_bounds__(512, 1) void gemm_ppp_kernel(PppArgs g) {
   const int GM = g.gm > 0 ? g.gm : 4;
   auto tile_mn = [&](int i, int& m0, int& n0) __attribute__((always_inline)) {
     const int wg = i < ndp ? lc + i * nwg : ndp * nwg + unit;
-    const int grp = wg / (GM * ntn), gm0 = grp * GM, gmn = min(GM, ntm - gm0), rem = wg - grp * GM * ntn;
-    m0 = (gm0 + rem % gmn) * 256;
-    n0 = (rem / gmn) * BN;
+    const int2 tl = raster_tile(wg, ntm, ntn, GM);
+    m0 = tl.x * 256;
+    n0 = tl.y * BN;
   };
 
   const __amdgpu_buffer_rsrc_t rA = rsrc(g.A, (unsigned)(((long)(g.M - 1) * g.lda + g.K) * 2));
@@ -205,7 +161,7 @@ __global__ __launch_bounds__(512, 1) void gemm_ppp_kernel(PppArgs g) {
   // DMA plan: instruction j of wave w fills piece rows j*64 + w*8 + lane/8,
   // physical chunk lane&7 <- logical chunk (lane&7) ^ ((row >> 1) & 7)
   const int prow = wave * 8 + (lane >> 3);
-  const int lcx = (lane & 7) ^ ((prow >> 1) & 7);
+  const int lcx = (lane & 7) ^ swz_chunk(prow);
   int voff[4][2];
   // piece p of tile (m0, n0): A pieces 0 (rows h=0) / 3 (h=1), B pieces 1 (h=0) / 2 (h=1)
   auto set_voff = [&](int p, int m0, int n0) __attribute__((always_inline)) {
@@ -266,8 +222,8 @@ __global__ __launch_bounds__(512, 1) void gemm_ppp_kernel(PppArgs g) {
     const int soff = kt * BK * 2;
     // K % 64 != 0: the last k-tile's chunks past K read zero (both operands)
     const bool live = gk < J && kt * BK + lcx * 8 < g.K;
-    dma16(r, dst, live ? voff[p][0] : (int)kOOB, soff);
-    if constexpr (p != 2 || NB1 == 2) dma16(r, dst + 64 * 128, live ? voff[p][1] : (int)kOOB, soff);
+    buf_dma16(r, dst, live ? voff[p][0] : (int)kOOB, soff);
+    if constexpr (p != 2 || NB1 == 2) buf_dma16(r, dst + 64 * 128, live ? voff[p][1] : (int)kOOB, soff);
   };
 
   const int fr = lane & 15, fq = lane >> 4;
@@ -289,7 +245,7 @@ __global__ __launch_bounds__(512, 1) void gemm_ppp_kernel(PppArgs g) {
 #pragma unroll
       for (int mi = 0; mi < 4; mi++) {
         floatx4& x = acc[2][mh * 4 + mi];
-        const unsigned x0 = cvt2(x[0], x[1]), x1 = cvt2(x[2], x[3]);
+        const unsigned x0 = pack2(x[0], x[1]), x1 = pack2(x[2], x[3]);
         const int m = m0 + wr * 128 + mh * 64 + mi * 16 + fr;
         const unsigned off = (m < g.M && nok) ? ((unsigned)m * (unsigned)g.ldc + (unsigned)n) * 2u : kOOB;
         if constexpr (NOST) asm volatile("" :: "v"(x0), "v"(x1), "v"(off));
@@ -312,15 +268,15 @@ __global__ __launch_bounds__(512, 1) void gemm_ppp_kernel(PppArgs g) {
       for (int mi = 0; mi < 4; mi++) {
         floatx4& x = acc[nh * 2][mh * 4 + mi];
         floatx4& y = acc[nh * 2 + 1][mh * 4 + mi];
-        const unsigned x0 = cvt2(fmaxf(x[0] + bx.x, 0.f), fmaxf(x[1] + bx.y, 0.f));
-        const unsigned x1 = cvt2(fmaxf(x[2] + bx.z, 0.f), fmaxf(x[3] + bx.w, 0.f));
-        const unsigned y0 = cvt2(fmaxf(y[0] + by.x, 0.f), fmaxf(y[1] + by.y, 0.f));
-        const unsigned y1 = cvt2(fmaxf(y[2] + by.z, 0.f), fmaxf(y[3] + by.w, 0.f));
+        const unsigned x0 = pack2(fmaxf(x[0] + bx.x, 0.f), fmaxf(x[1] + bx.y, 0.f));
+        const unsigned x1 = pack2(fmaxf(x[2] + bx.z, 0.f), fmaxf(x[3] + bx.w, 0.f));
+        const unsigned y0 = pack2(fmaxf(y[0] + by.x, 0.f), fmaxf(y[1] + by.y, 0.f));
+        const unsigned y1 = pack2(fmaxf(y[2] + by.z, 0.f), fmaxf(y[3] + by.w, 0.f));
         const auto s0 = __builtin_amdgcn_permlane16_swap(x0, y0, false, false);
         const auto s1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
         const int m = m0 + wr * 128 + mh * 64 + mi * 16 + fr;
         const unsigned off = (m < g.M && nok) ? ((unsigned)m * (unsigned)g.ldc + (unsigned)n) * 2u : kOOB;
-        store16(rC, off, make_uint4(s0[0], s1[0], s0[1], s1[1]));
+        bstore16(rC, off, make_uint4(s0[0], s1[0], s0[1], s1[1]));
         x = floatx4{0.f, 0.f, 0.f, 0.f};
         y = floatx4{0.f, 0.f, 0.f, 0.f};
       }
@@ -340,21 +296,21 @@ __global__ __launch_bounds__(512, 1) void gemm_ppp_kernel(PppArgs g) {
         const float zy0 = y[0] + by.x, zy1 = y[1] + by.y, zy2 = y[2] + by.z, zy3 = y[3] + by.w;
         const int m = m0 + wr * 128 + mh * 64 + mi * 16 + fr;
         const unsigned off = (m < g.M && nok) ? ((unsigned)m * (unsigned)g.ldc + (unsigned)n) * 2u : kOOB;
-        const unsigned px0 = cvt2(zx0, zx1), px1 = cvt2(zx2, zx3), py0 = cvt2(zy0, zy1), py1 = cvt2(zy2, zy3);
+        const unsigned px0 = pack2(zx0, zx1), px1 = pack2(zx2, zx3), py0 = pack2(zy0, zy1), py1 = pack2(zy2, zy3);
         {
           const auto s0 = __builtin_amdgcn_permlane16_swap(px0, py0, false, false);
           const auto s1 = __builtin_amdgcn_permlane16_swap(px1, py1, false, false);
-          store16(rC, off, make_uint4(s0[0], s1[0], s0[1], s1[1]));
+          bstore16(rC, off, make_uint4(s0[0], s1[0], s0[1], s1[1]));
         }
         {
           // GELU of the bf16-rounded z (exactly the value the backward's gelu'(z) reads)
           auto lo = [](unsigned w) { return __uint_as_float(w << 16); };
           auto hi = [](unsigned w) { return __uint_as_float(w & 0xffff0000u); };
-          const auto s0 = __builtin_amdgcn_permlane16_swap(cvt2(gelu_f(lo(px0)), gelu_f(hi(px0))),
-                                                            cvt2(gelu_f(lo(py0)), gelu_f(hi(py0))), false, false);
-          const auto s1 = __builtin_amdgcn_permlane16_swap(cvt2(gelu_f(lo(px1)), gelu_f(hi(px1))),
-                                                            cvt2(gelu_f(lo(py1)), gelu_f(hi(py1))), false, false);
-          store16(rY, off, make_uint4(s0[0], s1[0], s0[1], s1[1]));
+          const auto s0 = __builtin_amdgcn_permlane16_swap(pack2(gelu_f(lo(px0)), gelu_f(hi(px0))),
+                                                            pack2(gelu_f(lo(py0)), gelu_f(hi(py0))), false, false);
+          const auto s1 = __builtin_amdgcn_permlane16_swap(pack2(gelu_f(lo(px1)), gelu_f(hi(px1))),
+                                                            pack2(gelu_f(lo(py1)), gelu_f(hi(py1))), false, false);
+          bstore16(rY, off, make_uint4(s0[0], s1[0], s0[1], s1[1]));
         }
         x = floatx4{0.f, 0.f, 0.f, 0.f};
         y = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -365,8 +321,8 @@ __global__ __launch_bounds__(512, 1) void gemm_ppp_kernel(PppArgs g) {
     for (int mi = 0; mi < 4; mi++) {
       floatx4& x = acc[nh * 2][mh * 4 + mi];
       floatx4& y = acc[nh * 2 + 1][mh * 4 + mi];
-      unsigned x0 = cvt2(x[0], x[1]), x1 = cvt2(x[2], x[3]);
-      unsigned y0 = cvt2(y[0], y[1]), y1 = cvt2(y[2], y[3]);
+      unsigned x0 = pack2(x[0], x[1]), x1 = pack2(x[2], x[3]);
+      unsigned y0 = pack2(y[0], y[1]), y1 = pack2(y[2], y[3]);
       const auto s0 = __builtin_amdgcn_permlane16_swap(x0, y0, false, false);
       const auto s1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
       const int m = m0 + wr * 128 + mh * 64 + mi * 16 + fr;
@@ -376,7 +332,7 @@ __global__ __launch_bounds__(512, 1) void gemm_ppp_kernel(PppArgs g) {
         using V = decltype(__builtin_amdgcn_raw_buffer_load_b128(rC, 0, 0, 0));
         uint4 v = make_uint4(s0[0], s1[0], s0[1], s1[1]);
         __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<V*>(&v), rC, off, 0, 2);
-      } else store16(rC, off, make_uint4(s0[0], s1[0], s0[1], s1[1]));
+      } else bstore16(rC, off, make_uint4(s0[0], s1[0], s0[1], s1[1]));
       x = floatx4{0.f, 0.f, 0.f, 0.f};
       y = floatx4{0.f, 0.f, 0.f, 0.f};
     }
@@ -752,9 +708,7 @@ __global__ __launch_bounds__(512, 1) void gemm_ppw_kernel(PppArgs g) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
   const bool loader = wr == 0;  // group 0: DMA; group 1: stores
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, x8 = bid & 7;
-  const int lc = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (bid >> 3);
+  const int nwg = gridDim.x, lc = xcd_remap(blockIdx.x, nwg);
   ppp_stagger(g.stagger, lc);
   const int ntn = (g.N + BN - 1) / BN, ntm = (g.M + 255) / 256, ntiles = ntm * ntn;
   const int nk = (g.K + BK - 1) / BK;  // K % 8 == 0; a partial last k-tile reads zeros past K
@@ -768,9 +722,9 @@ __global__ __launch_bounds__(512, 1) void gemm_ppw_kernel(PppArgs g) {
   const int GM = g.gm > 0 ? g.gm : 4;
   auto tile_mn = [&](int i, int& m0, int& n0) __attribute__((always_inline)) {
     const int wg = lc + i * nwg;
-    const int grp = wg / (GM * ntn), gm0 = grp * GM, gmn = min(GM, ntm - gm0), rem = wg - grp * GM * ntn;
-    m0 = (gm0 + rem % gmn) * 256;
-    n0 = (rem / gmn) * BN;
+    const int2 tl = raster_tile(wg, ntm, ntn, GM);
+    m0 = tl.x * 256;
+    n0 = tl.y * BN;
   };
   const __amdgpu_buffer_rsrc_t rA = rsrc(g.A, (unsigned)(((long)(g.M - 1) * g.lda + g.K) * 2));
   const __amdgpu_buffer_rsrc_t rB = rsrc(g.B, (unsigned)(((long)(g.N - 1) * g.ldb + g.K) * 2));
@@ -778,7 +732,7 @@ __global__ __launch_bounds__(512, 1) void gemm_ppw_kernel(PppArgs g) {
   const __amdgpu_buffer_rsrc_t rZ = rsrc(DACT ? g.Zin : g.C, DACT ? g.c_bytes : 0u);
   // DMA plan (group 0): instruction j of wave w fills piece rows j*32 + w*8 + lane/8
   const int prow = wc * 8 + (lane >> 3);
-  const int lcx = (lane & 7) ^ ((prow >> 1) & 7);
+  const int lcx = (lane & 7) ^ swz_chunk(prow);
   int voff[4][DW];
   auto set_voff = [&](int p, int m0, int n0) __attribute__((always_inline)) {
     const int h = (p == 2 || p == 3) ? 1 : 0;
@@ -824,7 +778,7 @@ __global__ __launch_bounds__(512, 1) void gemm_ppw_kernel(PppArgs g) {
     const int soff = kt * BK * 2;
     const bool live = gk < J && kt * BK + lcx * 8 < g.K;  // K tail: chunks past K read zero
 #pragma unroll
-    for (int j = 0; j < DW; j++) dma16(r, dst + j * 32 * 128, live ? voff[p][j] : (int)kOOB, soff);
+    for (int j = 0; j < DW; j++) buf_dma16(r, dst + j * 32 * 128, live ? voff[p][j] : (int)kOOB, soff);
   };
   const int fr = lane & 15, fq = lane >> 4;
   const int ro0 = fr * 128 + ((fq ^ (fr >> 1)) << 4), ro1 = fr * 128 + (((4 + fq) ^ (fr >> 1)) << 4);
@@ -841,8 +795,8 @@ __global__ __launch_bounds__(512, 1) void gemm_ppw_kernel(PppArgs g) {
     for (int mi = 0; mi < 4; mi++) {
       floatx4& x = acc[nh * 2][mh * 4 + mi];
       floatx4& y = acc[nh * 2 + 1][mh * 4 + mi];
-      const unsigned x0 = cvt2(x[0], x[1]), x1 = cvt2(x[2], x[3]);
-      const unsigned y0 = cvt2(y[0], y[1]), y1 = cvt2(y[2], y[3]);
+      const unsigned x0 = pack2(x[0], x[1]), x1 = pack2(x[2], x[3]);
+      const unsigned y0 = pack2(y[0], y[1]), y1 = pack2(y[2], y[3]);
       const auto s0 = __builtin_amdgcn_permlane16_swap(x0, y0, false, false);
       const auto s1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
       v[mi] = make_uint4(s0[0], s1[0], s0[1], s1[1]);
@@ -1146,9 +1100,9 @@ __global__ __launch_bounds__(512, 1) void gemm_ppw_kernel(PppArgs g) {
 #if KFA_PW_STAMP
   PW_ST(21);
   psum[22] = (unsigned)J;
-  if (lane == 0 && bid < 256 && (wave & 3) == 0) {
+  if (lane == 0 && blockIdx.x < 256 && (wave & 3) == 0) {
 #pragma unroll
-    for (int i = 0; i < kPwSeg; i++) g_pw_stamps[(bid * 2 + wr) * kPwSeg + i] = psum[i];
+    for (int i = 0; i < kPwSeg; i++) g_pw_stamps[(blockIdx.x * 2 + wr) * kPwSeg + i] = psum[i];
   }
 #endif
 }
@@ -1187,9 +1141,7 @@ __global__ __launch_bounds__(512, 1) void gemm_ppw3_kernel(PppArgs g) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
   const bool loader = wr == 0;
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, x8 = bid & 7;
-  const int lc = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (bid >> 3);
+  const int nwg = gridDim.x, lc = xcd_remap(blockIdx.x, nwg);
   const int ntn = (g.N + BN - 1) / BN, ntm = (g.M + 255) / 256, ntiles = ntm * ntn;
   const int nk = (g.K + BK - 1) / BK;
   const int my_tiles = lc < ntiles ? (ntiles - 1 - lc) / nwg + 1 : 0;
@@ -1198,15 +1150,15 @@ __global__ __launch_bounds__(512, 1) void gemm_ppw3_kernel(PppArgs g) {
   const int GM = g.gm > 0 ? g.gm : 4;
   auto tile_mn = [&](int i, int& m0, int& n0) __attribute__((always_inline)) {
     const int wg = lc + i * nwg;
-    const int grp = wg / (GM * ntn), gm0 = grp * GM, gmn = min(GM, ntm - gm0), rem = wg - grp * GM * ntn;
-    m0 = (gm0 + rem % gmn) * 256;
-    n0 = (rem / gmn) * BN;
+    const int2 tl = raster_tile(wg, ntm, ntn, GM);
+    m0 = tl.x * 256;
+    n0 = tl.y * BN;
   };
   const __amdgpu_buffer_rsrc_t rA = rsrc(g.A, (unsigned)(((long)(g.M - 1) * g.lda + g.K) * 2));
   const __amdgpu_buffer_rsrc_t rB = rsrc(g.B, (unsigned)(((long)(g.N - 1) * g.ldb + g.K) * 2));
   const __amdgpu_buffer_rsrc_t rC = rsrc(g.C, g.c_bytes);
   const int prow = wc * 8 + (lane >> 3);
-  const int lcx = (lane & 7) ^ ((prow >> 1) & 7);
+  const int lcx = (lane & 7) ^ swz_chunk(prow);
   int voff[4][DW];  // piece 2 uses entries 0-1 only (the compiler drops the rest)
   // pieces: 0 = A rows {0-63, 128-191}, 3 = A rows {64-127, 192-255}, 1 = the first 32
   // columns of each wave column group (128 rows), 2 = their third 16-column block (64 rows)
@@ -1258,7 +1210,7 @@ __global__ __launch_bounds__(512, 1) void gemm_ppw3_kernel(PppArgs g) {
     const int soff = kt * BK * 2;
     const bool live = gk < J && kt * BK + lcx * 8 < g.K;
 #pragma unroll
-    for (int j = 0; j < nd; j++) dma16(r, dst + j * 32 * 128, live ? voff[p][j] : (int)kOOB, soff);
+    for (int j = 0; j < nd; j++) buf_dma16(r, dst + j * 32 * 128, live ? voff[p][j] : (int)kOOB, soff);
   };
   const int fr = lane & 15, fq = lane >> 4;
   const int ro0 = fr * 128 + ((fq ^ (fr >> 1)) << 4), ro1 = fr * 128 + (((4 + fq) ^ (fr >> 1)) << 4);
@@ -1282,8 +1234,8 @@ __global__ __launch_bounds__(512, 1) void gemm_ppw3_kernel(PppArgs g) {
     for (int mi = 0; mi < 4; mi++) {
       floatx4& x = acc[0][mh * 4 + mi];
       floatx4& y = acc[1][mh * 4 + mi];
-      const unsigned x0 = cvt2(x[0], x[1]), x1 = cvt2(x[2], x[3]);
-      const unsigned y0 = cvt2(y[0], y[1]), y1 = cvt2(y[2], y[3]);
+      const unsigned x0 = pack2(x[0], x[1]), x1 = pack2(x[2], x[3]);
+      const unsigned y0 = pack2(y[0], y[1]), y1 = pack2(y[2], y[3]);
       const auto s0 = __builtin_amdgcn_permlane16_swap(x0, y0, false, false);
       const auto s1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
       v[mi] = make_uint4(s0[0], s1[0], s0[1], s1[1]);
@@ -1298,7 +1250,7 @@ __global__ __launch_bounds__(512, 1) void gemm_ppw3_kernel(PppArgs g) {
     for (int k = 0; k < 4; k++) {
       floatx4& x = acc[2][2 * k];
       floatx4& y = acc[2][2 * k + 1];
-      v[k] = make_uint4(cvt2(x[0], x[1]), cvt2(x[2], x[3]), cvt2(y[0], y[1]), cvt2(y[2], y[3]));
+      v[k] = make_uint4(pack2(x[0], x[1]), pack2(x[2], x[3]), pack2(y[0], y[1]), pack2(y[2], y[3]));
       x = floatx4{0.f, 0.f, 0.f, 0.f};
       y = floatx4{0.f, 0.f, 0.f, 0.f};
     }
@@ -1506,17 +1458,6 @@ KFA_API int kfa_pw_stamps(unsigned* out, int n) {
 }
 #endif
 
-int ppp_cus() {
-  static int c = 0;
-  if (!c) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-    if (c <= 0) c = 256;
-  }
-  return c;
-}
-
 }  // namespace
 
 // C = A · Bᵀ (bf16 out) on the persistent ping-pong kernel.  K % 8 == 0 (a
@@ -1544,7 +1485,7 @@ static int ppp_split(long tiles, long cus, int nk) {
 KFA_API long kfa_gemm_ppp_ws_bytes(int M, int N, int K, int bn, int blocks) {
   if (bn == 0) bn = kfa_gemm_ppp_pick_bn(M, N);
   const long tiles = (long)((M + 255) / 256) * ((N + bn - 1) / bn);
-  const long cus = blocks > 0 ? blocks : ppp_cus();
+  const long cus = blocks > 0 ? blocks : kfa_cu_count();
   if (tiles <= 0 || K % 8) return 0;
   const int s = ppp_split(tiles, cus, (K + BK - 1) / BK);
   if (s == 1) return 0;
@@ -1553,7 +1494,7 @@ KFA_API long kfa_gemm_ppp_ws_bytes(int M, int N, int K, int bn, int blocks) {
 }
 
 KFA_API int kfa_gemm_ppp_pick_bn(int M, int N) {
-  const long cus = ppp_cus();
+  const long cus = kfa_cu_count();
   if (N % 192) return 256;
   const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256), t192 = (long)((M + 255) / 256) * (N / 192);
   // rounds of the persistent grid, in 256-wide tile units of work
@@ -1580,87 +1521,75 @@ static inline PppArgs with_gm(PppArgs a) {
   return a;
 }
 
-// Z = A · Bᵀ + bias (bf16, the pre-activation), Y = gelu(Z) on the persistent kernel with
-// the bias + GELU epilogue (256-wide tiles, no split): K % 8 == 0, K >= 128, N % 8 == 0,
-// N <= 8192; Z and Y share ldc.  Returns 0, -1 on unsupported operands.
-KFA_API int kfa_gemm_ppp_gelu(const bf16_t* A, const bf16_t* B, bf16_t* Z, bf16_t* Y, const float* bias, int M, int N,
-                              int K, int lda, int ldb, int ldc, hipStream_t st) {
+// The activation entry points below share their operand rules (256-wide tiles, no split):
+// K % 8 == 0, K >= 128, N % 8 == 0, strides % 8 == 0, every extent within 31-bit buffer
+// offsets, plus `ok`, the entry point's own requirements.  Fills g (C = bias + product
+// target, no Y / Zin) and returns the grid; 0: empty problem, -1: unsupported operands,
+// -2: an extent past 31 bits.
+static int ppp_act_args(PppArgs& g, const bf16_t* A, const bf16_t* B, bf16_t* C, const float* bias, int M, int N, int K,
+                        int lda, int ldb, int ldc, bool ok) {
   if (M <= 0 || N <= 0) return 0;
-  if (K < 2 * BK || K % 8 || N % 8 || N > 8192 || lda % 8 || ldb % 8 || ldc % 8 || lda < K || ldb < K || ldc < N ||
-      !bias || !Y)
-    return -1;
+  if (K < 2 * BK || K % 8 || N % 8 || lda % 8 || ldb % 8 || ldc % 8 || lda < K || ldb < K || ldc < N || !ok) return -1;
   const long cb = (long)M * ldc * 2;
   if (cb >= (long)kOOB || (long)M * lda * 2 >= (long)kOOB || (long)N * ldb * 2 >= (long)kOOB) return -2;
   const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
-  const long cus = ppp_cus();
-  const int grid = (int)(tiles < cus ? tiles : cus);
-  const PppArgs g{A, B, Z, M, N, K, lda, ldb, ldc, (unsigned)cb, nullptr, nullptr, 1, g_stagger, Y, bias};
-  hipLaunchKernelGGL((gemm_ppp_kernel<256, false, 0, false, 1>), dim3(grid), dim3(512), 0, st, with_gm(g));
+  const long cus = kfa_cu_count();
+  g = with_gm(PppArgs{A, B, C, M, N, K, lda, ldb, ldc, (unsigned)cb, nullptr, nullptr, 1, g_stagger, nullptr, bias});
+  return (int)(tiles < cus ? tiles : cus);
+}
+
+// Z = A · Bᵀ + bias (bf16, the pre-activation), Y = gelu(Z) on the persistent kernel with
+// the bias + GELU epilogue; N <= 8192 (the bias is staged in 32 KB of LDS); Z and Y share ldc.
+KFA_API int kfa_gemm_ppp_gelu(const bf16_t* A, const bf16_t* B, bf16_t* Z, bf16_t* Y, const float* bias, int M, int N,
+                              int K, int lda, int ldb, int ldc, hipStream_t st) {
+  PppArgs g;
+  const int grid = ppp_act_args(g, A, B, Z, bias, M, N, K, lda, ldb, ldc, N <= 8192 && bias && Y);
+  if (grid <= 0) return grid;
+  g.Y = Y;
+  hipLaunchKernelGGL((gemm_ppp_kernel<256, false, 0, false, 1>), dim3(grid), dim3(512), 0, st, g);
   return kfa_status();
 }
 
 // Y = relu(A · Bᵀ + bias) (bf16) on the persistent kernel with the bias + ReLU epilogue
-// (256-wide tiles, no split; the pre-activation is not written): same operand rules as
-// kfa_gemm_ppp_gelu.  Returns 0, -1 on unsupported operands.
+// (the pre-activation is not written); N <= 8192 as kfa_gemm_ppp_gelu.
 KFA_API int kfa_gemm_ppp_relu(const bf16_t* A, const bf16_t* B, bf16_t* Y, const float* bias, int M, int N, int K,
                               int lda, int ldb, int ldc, hipStream_t st) {
-  if (M <= 0 || N <= 0) return 0;
-  if (K < 2 * BK || K % 8 || N % 8 || N > 8192 || lda % 8 || ldb % 8 || ldc % 8 || lda < K || ldb < K || ldc < N ||
-      !bias || !Y)
-    return -1;
-  const long cb = (long)M * ldc * 2;
-  if (cb >= (long)kOOB || (long)M * lda * 2 >= (long)kOOB || (long)N * ldb * 2 >= (long)kOOB) return -2;
-  const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
-  const long cus = ppp_cus();
-  const int grid = (int)(tiles < cus ? tiles : cus);
-  const PppArgs g{A, B, Y, M, N, K, lda, ldb, ldc, (unsigned)cb, nullptr, nullptr, 1, g_stagger, nullptr, bias};
-  hipLaunchKernelGGL((gemm_ppp_kernel<256, false, 0, false, 2>), dim3(grid), dim3(512), 0, st, with_gm(g));
+  PppArgs g;
+  const int grid = ppp_act_args(g, A, B, Y, bias, M, N, K, lda, ldb, ldc, N <= 8192 && bias && Y);
+  if (grid <= 0) return grid;
+  hipLaunchKernelGGL((gemm_ppp_kernel<256, false, 0, false, 2>), dim3(grid), dim3(512), 0, st, g);
   return kfa_status();
 }
 
 // Y = relu(A · Bᵀ + bias) (bf16) on the wave-specialised persistent kernel (gemm_ppw_kernel
-// <NT, false, 2>: the bias added to the bf16 product by the store waves); nt: non-temporal
-// stores.  Same operand rules as kfa_gemm_ppp_relu.  Returns 0, -1 on unsupported operands.
+// <NT, false, 2>: the bias added to the bf16 product by the store waves, read from global
+// memory: any N); nt: non-temporal stores.
 KFA_API int kfa_gemm_ppw_relu(const bf16_t* A, const bf16_t* B, bf16_t* Y, const float* bias, int M, int N, int K,
                               int lda, int ldb, int ldc, int nt, hipStream_t st) {
-  if (M <= 0 || N <= 0) return 0;
-  if (K < 2 * BK || K % 8 || N % 8 || lda % 8 || ldb % 8 || ldc % 8 || lda < K || ldb < K || ldc < N || !bias ||
-      !Y)
-    return -1;
-  const long cb = (long)M * ldc * 2;
-  if (cb >= (long)kOOB || (long)M * lda * 2 >= (long)kOOB || (long)N * ldb * 2 >= (long)kOOB) return -2;
-  const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
-  const long cus = ppp_cus();
-  const int grid = (int)(tiles < cus ? tiles : cus);
-  const PppArgs g{A, B, Y, M, N, K, lda, ldb, ldc, (unsigned)cb, nullptr, nullptr, 1, g_stagger, nullptr, bias};
-  if (nt) hipLaunchKernelGGL((gemm_ppw_kernel<true, false, 2>), dim3(grid), dim3(512), 0, st, with_gm(g));
-  else hipLaunchKernelGGL((gemm_ppw_kernel<false, false, 2>), dim3(grid), dim3(512), 0, st, with_gm(g));
+  PppArgs g;
+  const int grid = ppp_act_args(g, A, B, Y, bias, M, N, K, lda, ldb, ldc, bias && Y);
+  if (grid <= 0) return grid;
+  if (nt) hipLaunchKernelGGL((gemm_ppw_kernel<true, false, 2>), dim3(grid), dim3(512), 0, st, g);
+  else hipLaunchKernelGGL((gemm_ppw_kernel<false, false, 2>), dim3(grid), dim3(512), 0, st, g);
   return kfa_status();
 }
 
 // dz = (A · Bᵀ) * gelu'(Zin + bias) (bf16; bias fp32 [N] or null) on the wave-specialised
 // persistent kernel with the GELU-backward epilogue; dbias (fp32 [N], nullable) (+)= the
 // column sums of dz (via cpart: kfa_gemm_ppw_dact_part_floats(M, N) floats of scratch).
-// K % 8 == 0, K >= 128, N % 8 == 0; Zin shares C's ldc.  Returns 0, -1 on unsupported operands.
+// Zin shares C's ldc.
 KFA_API long kfa_gemm_ppw_dact_part_floats(int M, int N) { return (long)((M + 63) / 64) * N; }
 
 KFA_API int kfa_gemm_ppw_dact(const bf16_t* A, const bf16_t* B, bf16_t* C, const bf16_t* Zin, const float* bias,
                               float* cpart, float* dbias, int accumulate, int M, int N, int K, int lda, int ldb,
                               int ldc, int nt, hipStream_t st) {
-  if (M <= 0 || N <= 0) return 0;
-  if (K < 2 * BK || K % 8 || N % 8 || lda % 8 || ldb % 8 || ldc % 8 || lda < K || ldb < K || ldc < N || !Zin ||
-      (dbias && !cpart))
-    return -1;
-  const long cb = (long)M * ldc * 2;
-  if (cb >= (long)kOOB || (long)M * lda * 2 >= (long)kOOB || (long)N * ldb * 2 >= (long)kOOB) return -2;
-  const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
-  const long cus = ppp_cus();
-  PppArgs g{A, B, C, M, N, K, lda, ldb, ldc, (unsigned)cb, nullptr, nullptr, 1, g_stagger, nullptr, bias};
+  PppArgs g;
+  const int grid = ppp_act_args(g, A, B, C, bias, M, N, K, lda, ldb, ldc, Zin && (!dbias || cpart));
+  if (grid <= 0) return grid;
   g.Zin = Zin;
   g.cpart = dbias ? cpart : nullptr;
-  const int grid = (int)(tiles < cus ? tiles : cus);
-  if (nt) hipLaunchKernelGGL((gemm_ppw_kernel<true, true>), dim3(grid), dim3(512), 0, st, with_gm(g));
-  else hipLaunchKernelGGL((gemm_ppw_kernel<false, true>), dim3(grid), dim3(512), 0, st, with_gm(g));
+  if (nt) hipLaunchKernelGGL((gemm_ppw_kernel<true, true>), dim3(grid), dim3(512), 0, st, g);
+  else hipLaunchKernelGGL((gemm_ppw_kernel<false, true>), dim3(grid), dim3(512), 0, st, g);
   if (dbias)
     hipLaunchKernelGGL(colpart_reduce, dim3((N + 63) / 64), dim3(256), 0, st, cpart, (M + 63) / 64, N, dbias,
                        accumulate);
@@ -1677,7 +1606,7 @@ KFA_API int kfa_gemm_ppp(const bf16_t* A, const bf16_t* B, bf16_t* C, int M, int
   if (bn == 0) bn = kfa_gemm_ppp_pick_bn(M, N);
   if (bn != 256 && bn != 192) return -1;
   const long tiles = (long)((M + 255) / 256) * ((N + bn - 1) / bn);
-  const long cus = blocks > 0 ? blocks : ppp_cus();
+  const long cus = blocks > 0 ? blocks : kfa_cu_count();
   int split = nosplit ? 1 : ppp_split(tiles, cus, (K + BK - 1) / BK);
   if (split > 1 && (ws == nullptr || ws_bytes < kfa_gemm_ppp_ws_bytes(M, N, K, bn, blocks))) return -3;
   // a split grid is the whole `cus` blocks (the split units fill the last round)

@@ -25,12 +25,13 @@
 // source address), double-buffered, one barrier pair per 64-deep k-step; rows
 // past M and k past K read as zero through the buffer range check.
 #include "common.h"
+#include "tile.h"
 
 namespace {
+using namespace tile;
 
 constexpr int BK = 64;
 constexpr int BM = 256, BN = 64;
-constexpr unsigned kOOB = 0x80000000u;
 
 struct SkArgs {
   const bf16_t* A;
@@ -42,17 +43,6 @@ struct SkArgs {
   float* ws;   // [tiles][S][16 floatx4][256 threads]
   int* cnt;    // [tiles] tickets, zero on entry and on exit
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* lds, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
-
-// element offset of (row, 16-B chunk) in a [rows][BK] LDS image, chunk XOR-swizzled
-__device__ __forceinline__ int swz(int row, int chunk) { return row * BK + ((chunk ^ ((row >> 1) & 7)) << 3); }
 
 __global__ __launch_bounds__(256, 2) void gemm_skinny_kernel(SkArgs g) {
   __shared__ __attribute__((aligned(16))) bf16_t smem[2 * (BM + BN) * BK];  // 80 KB: two k-steps of A and B
@@ -73,14 +63,14 @@ __global__ __launch_bounds__(256, 2) void gemm_skinny_kernel(SkArgs g) {
 #pragma unroll
   for (int i = 0; i < 8; i++) {
     const int row = 8 * (4 * i + wave) + lr;
-    const int ck = (lane & 7) ^ ((row >> 1) & 7);
+    const int ck = (lane & 7) ^ swz_chunk(row);
     a_ck[i] = ck * 8;
     a_off[i] = m0 + row < g.M ? ((m0 + row) * g.lda + kb + ck * 8) * 2 : (int)kOOB;
   }
 #pragma unroll
   for (int i = 0; i < 2; i++) {
     const int row = 8 * (4 * i + wave) + lr, n = n0 + row;
-    const int ck = (lane & 7) ^ ((row >> 1) & 7);
+    const int ck = (lane & 7) ^ swz_chunk(row);
     b_ck[i] = ck * 8;
     b_off[i] = n < g.N ? (n * g.ldb + kb + ck * 8) * 2 : (int)kOOB;
   }
@@ -91,12 +81,12 @@ __global__ __launch_bounds__(256, 2) void gemm_skinny_kernel(SkArgs g) {
 #pragma unroll
     for (int i = 0; i < 8; i++) {
       const bool ok = k + a_ck[i] < klen;  // k tail past the slice (and K) reads zero
-      dma16(rA, As + 8 * (4 * i + wave) * BK * 2, ok ? a_off[i] : (int)kOOB, k * 2);
+      buf_dma16(rA, As + 8 * (4 * i + wave) * BK * 2, ok ? a_off[i] : (int)kOOB, k * 2);
     }
 #pragma unroll
     for (int i = 0; i < 2; i++) {
       const bool ok = k + b_ck[i] < klen;
-      dma16(rB, Bs + 8 * (4 * i + wave) * BK * 2, ok ? b_off[i] : (int)kOOB, k * 2);
+      buf_dma16(rB, Bs + 8 * (4 * i + wave) * BK * 2, ok ? b_off[i] : (int)kOOB, k * 2);
     }
   };
 
@@ -121,16 +111,16 @@ __global__ __launch_bounds__(256, 2) void gemm_skinny_kernel(SkArgs g) {
     for (int ks = 0; ks < 2; ks++) {
       short8 af[4], bf[4];
 #pragma unroll
-      for (int i = 0; i < 4; i++) af[i] = *reinterpret_cast<const short8*>(Ab + swz(wave * 64 + i * 16 + fr, ks * 4 + fq));
+      for (int i = 0; i < 4; i++) af[i] = *reinterpret_cast<const short8*>(Ab + swz128(wave * 64 + i * 16 + fr, ks * 4 + fq));
 #pragma unroll
-      for (int i = 0; i < 4; i++) bf[i] = *reinterpret_cast<const short8*>(Bb + swz(i * 16 + fr, ks * 4 + fq));
+      for (int i = 0; i < 4; i++) bf[i] = *reinterpret_cast<const short8*>(Bb + swz128(i * 16 + fr, ks * 4 + fq));
 #pragma unroll
       for (int ni = 0; ni < 4; ni++)
 #pragma unroll
         for (int mi = 0; mi < 4; mi++)
           acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[ni], af[mi], acc[ni][mi], 0, 0, 0);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // buf free for step t+2's DMA
+    lds_barrier();  // buf free for step t+2's DMA
   }
 
   // acc[ni][mi][r] = C(m = 64 wave + 16 mi + fr, n = n0 + 16 ni + 4 fq + r)
@@ -190,23 +180,12 @@ __global__ __launch_bounds__(256, 2) void gemm_skinny_kernel(SkArgs g) {
   }
 }
 
-int sk_cus() {
-  static int c = 0;
-  if (!c) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-    if (c <= 0) c = 256;
-  }
-  return c;
-}
-
 // slices per tile: about one block per CU in total, each slice >= 2 k-steps
 // (tiles = 256 x 64 output tiles over every 256-row band)
 void sk_plan(int M, int N, int K, int want_splits, int& tiles, int& S, int& kchunk) {
   tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   const int nks = (K + BK - 1) / BK;
-  S = want_splits > 0 ? want_splits : sk_cus() / tiles;
+  S = want_splits > 0 ? want_splits : kfa_cu_count() / tiles;
   if (S > nks / 2) S = nks / 2;
   if (S < 1) S = 1;
   const int per = (nks + S - 1) / S;

@@ -8,7 +8,7 @@
 // both operands: dY and X are stored channel-contiguous, so a k-slice of either
 // operand arrives as [k][channel] rows.  MFMA wants each lane's 8 k-values of
 // one row/column, i.e. the transpose — CDNA4's ds_read_b64_tr_b16 (T10) does
-// it in the LDS read: tiles are DMA'd (global_load_lds, 16 B/lane) lane-linear
+// it in the LDS read: tiles are DMA'd (LDS-DMA, 16 B/lane) lane-linear
 // into [k][128]-element images with the conflict-free XOR swizzle
 //   off(row, chunk) = 256*row + 16*(chunk ^ (((row&3)<<2) | ((row>>2)&3)))
 // applied on the per-lane SOURCE address, and each MFMA operand is two
@@ -24,8 +24,10 @@
 #include <utility>
 
 #include "common.h"
+#include "tile.h"
 
 namespace {
+using namespace tile;
 
 constexpr int BKW = 64;
 
@@ -37,34 +39,15 @@ struct WGeo {
   unsigned x_bytes;  // extent of X (buffer range)
 };
 
-__device__ __forceinline__ int fdiv(int x, int d, float rcp) {
-  int q = (int)((float)x * rcp);
-  const int r = x - q * d;
-  q += (r >= d) - (r < 0);
-  return q;
-}
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-constexpr unsigned kOOB = 0x80000000u;  // a buffer offset past every extent: the load returns 0
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wrsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-// 16 B per lane buffer -> LDS DMA; a plain device function (the builtin inside the
-// templated kernel's lambda stops clang's host pass from emitting launch stubs)
 #ifndef KFA_WG_PART_ST_NT
 #define KFA_WG_PART_ST_NT 0  // A/B: split-K partial stores non-temporal
 #endif
 #ifndef KFA_WG_DY_AUX
-#define KFA_WG_DY_AUX 0
+#define KFA_WG_DY_AUX 0  // cache policy of the dY operand's DMA
 #endif
 #ifndef KFA_WG_X_AUX
-#define KFA_WG_X_AUX 0
+#define KFA_WG_X_AUX 0  // ... and of the X operand's
 #endif
-template <int AUX = 0>
-__device__ __forceinline__ void buf_dma16(__amdgpu_buffer_rsrc_t r, bf16_t* lds, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, AUX);
-}
 
 typedef short v4i16 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
@@ -193,8 +176,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wgrad_kernel(const bf16_t* __
   const int PQ = g.P * g.Q;
   const float rPQ = 1.f / (float)PQ, rQ = 1.f / (float)g.Q;
   const bool lin_b = g.R == 1 && g.S == 1 && g.st == 1 && g.pad == 0;  // X row k is pixel k
-  const __amdgpu_buffer_rsrc_t rA = wrsrc(dY, (unsigned)g.K * (unsigned)g.Co * 2u);
-  const __amdgpu_buffer_rsrc_t rX = wrsrc(X, g.x_bytes);
+  const __amdgpu_buffer_rsrc_t rA = rsrc(dY, (unsigned)g.K * (unsigned)g.Co * 2u);
+  const __amdgpu_buffer_rsrc_t rX = rsrc(X, g.x_bytes);
   int a_vo[A_IPW], b_vo[B_IPW];
 #pragma unroll
   for (int i = 0; i < A_IPW; i++) a_vo[i] = a_ok[i] ? (a_row[i] * g.Co + a_m[i]) * 2 : (int)kOOB;
@@ -318,18 +301,18 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wgrad_kernel(const bf16_t* __
       // outstanding (the 4-bit counter caps the count at 15: a read more is waited for)
       constexpr int RH = 2 * (TM + TN) < 15 ? 2 * (TM + TN) : 15;
       rd_ks(std::integral_constant<int, 1>{});
-      asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(RH) : "memory");
+      lgkm_wait<RH>();
       __builtin_amdgcn_sched_barrier(0);
       mfma_ks(0);
       __builtin_amdgcn_sched_barrier(0);
     } else {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      lgkm_wait<0>();
       __builtin_amdgcn_sched_barrier(0);
       mfma_ks(0);
       __builtin_amdgcn_sched_barrier(0);
       rd_ks(std::integral_constant<int, 1>{});
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm_wait<0>();
     __builtin_amdgcn_sched_barrier(0);
     mfma_ks(1);
     __builtin_amdgcn_sched_barrier(0);
@@ -386,22 +369,6 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wgrad_kernel(const bf16_t* __
 // (accumulating) write into the gradient.
 constexpr int WP_BK = 64;
 constexpr int WP_PIECE = WP_BK * 128 * 2;  // 64 k-rows x 128 channels, bytes
-
-template <int N>
-__device__ __forceinline__ void wp_vmcnt() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-}
-__device__ __forceinline__ void wp_retire(int younger) {  // all but the pieces of the `younger` newest phases
-  if (younger >= 4) wp_vmcnt<8>();
-  else if (younger == 3) wp_vmcnt<6>();
-  else if (younger == 2) wp_vmcnt<4>();
-  else if (younger == 1) wp_vmcnt<2>();
-  else wp_vmcnt<0>();
-}
 
 // Diagnostic build only (KFA_WP_STAMP=1: three segments per phase, 2: five):
 // per-segment s_memtime cycle sums of the k-loop of blocks 0..255, waves 0 and 4
@@ -461,8 +428,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_pp_kernel(const bf16_t* __restri
   unsigned long long wlast = wp_now();
 #endif
 
-  const __amdgpu_buffer_rsrc_t rA = wrsrc(dY, (unsigned)g.K * (unsigned)g.Co * 2u);
-  const __amdgpu_buffer_rsrc_t rB = wrsrc(X, GATHER ? g.x_bytes : (unsigned)g.K * (unsigned)g.Ci * 2u);
+  const __amdgpu_buffer_rsrc_t rA = rsrc(dY, (unsigned)g.K * (unsigned)g.Co * 2u);
+  const __amdgpu_buffer_rsrc_t rB = rsrc(X, GATHER ? g.x_bytes : (unsigned)g.K * (unsigned)g.Ci * 2u);
   // DMA plan: instruction j (0, 1) of wave w fills piece rows 4 (2w + j) + lane / 16,
   // physical chunk lane & 15 <- logical chunk (lane & 15) ^ img_swz<128>(row)
   int voff[4][2];
@@ -512,7 +479,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_pp_kernel(const bf16_t* __restri
           const int hh = gk_p[j] * g.st + (gx_rs[j] >> 16), ww = gk_q[j] * g.st + (int)(short)(gx_rs[j] & 0xffff);
           const bool ok = gk_img[j] < nimg && (unsigned)hh < (unsigned)g.H && (unsigned)ww < (unsigned)g.W;
           const int vo = ok ? (((gk_img[j] * g.H + hh) * g.W + ww) * g.Ci + gx_ci[j] + h * 32) * 2 : (int)kOOB;
-          buf_dma16<0>(rB, reinterpret_cast<bf16_t*>(dst + j * 1024), vo, 0);
+          buf_dma16(rB, dst + j * 1024, vo, 0);
           if constexpr (h == 1) {  // B1 closes this k-tile's X rows: advance them 64 pixels
             int q = gk_q[j] + dq, pp = gk_p[j] + dp, img = gk_img[j] + dimg;
             if (q >= g.Q) { q -= g.Q; pp++; }
@@ -524,17 +491,17 @@ __global__ __launch_bounds__(512, 1) void wgrad_pp_kernel(const bf16_t* __restri
         }
       } else {
         const int soff = (kb + kt * WP_BK) * (isA ? g.Co : g.Ci) * 2;
-        buf_dma16<0>(isA ? rA : rB, reinterpret_cast<bf16_t*>(dst), voff[p][0], soff);
-        buf_dma16<0>(isA ? rA : rB, reinterpret_cast<bf16_t*>(dst + 1024), voff[p][1], soff);
+        buf_dma16(isA ? rA : rB, dst, voff[p][0], soff);
+        buf_dma16(isA ? rA : rB, dst + 1024, voff[p][1], soff);
       }
     }
   };
   auto retire = [&](int P, auto steady) __attribute__((always_inline)) {
     if constexpr (decltype(steady)::value) {
-      wp_vmcnt<8>();
+      vm_wait<8>();
     } else {
       const int younger = min(P, plast) - (P - 3) + 1;
-      wp_retire(younger < 0 ? 0 : younger);
+      tile::retire(younger < 0 ? 0 : younger);
     }
   };
 
@@ -805,17 +772,6 @@ const bf16_t* zero_page() {
   return z;
 }
 
-int num_cus() {
-  static int cached = 0;
-  if (!cached) {
-    int dev = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&cached, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cached <= 0) cached = 256;
-  }
-  return cached;
-}
-
 // 64x256 tiles for the Co = 64 weights (stem, 256->64 1x1s): KFA_WGRAD_WIDE64=0 keeps 64x128
 bool wide64() {
   static int v = -1;
@@ -878,7 +834,7 @@ static bool pp_shape(long K, int Co, int N, bool pointwise, int Ci = 0, int H = 
   // chip (no split-K): the BERT MLM decoder, 5120 x 30528 x 768, 320.6 -> 286.8 us
   const long tiles = (long)((Co + 255) / 256) * ((N + 255) / 256);
   return wgrad_pp_mode() == 2 ? (Co >= 128 && N >= 128)
-                              : (Co >= 256 && N >= 256 && (K >= 8192 || tiles >= num_cus()));
+                              : (Co >= 256 && N >= 256 && (K >= 8192 || tiles >= kfa_cu_count()));
 }
 
 WPlan plan(long K, int Co, int N, bool pointwise = false) {
@@ -896,7 +852,7 @@ WPlan plan(long K, int Co, int N, bool pointwise = false) {
   // one wave of blocks, each >= 4 k-steps; big-weight layers run
   // without split-K and accumulate in the epilogue (no partial round trip)
   const long steps = (K + BKW - 1) / BKW;
-  long splits = ((long)p.blocks_per_cu * num_cus()) / p.tiles;
+  long splits = ((long)p.blocks_per_cu * kfa_cu_count()) / p.tiles;
   splits = splits < 1 ? 1 : splits;
   // each split >= min_steps k-steps (KFA_WGRAD_MIN_STEPS, default 4): more steps per
   // split = fewer fp32 partial slabs to write and reduce, at the cost of idle CUs
