@@ -869,6 +869,213 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(const bf16_t* __restric
                                                 er);
 }
 
+// ---------------------------------------------------------------------------
+// Halo-staged implicit GEMM: stride-1 3x3 'same' convs with C = 64 / 128 (forward
+// and the stride-1 dgrad: ra = +-1).  conv_igemm_kernel moves every input pixel
+// L2 -> LDS once per tap (9x); the nine taps of a linear tile of BM output pixels
+// m0 .. m0+BM-1 read the input pixels m0-(W+1) .. m0+BM-1+(W+1), so this kernel
+// stages that run ONCE per tile (HR = BM + 2(W+1) rows, 1.23-1.45x the tile) and
+// tap (r, s)'s A fragment of tile row i is LDS row i + (W+1) + dh*W + dw.
+// Image: C/64 sub-images of [HRP][128 B] rows, chunk ^= halo_swz(row) keyed on
+// the LDS row's own index.  Pixels before the tensor / past its end stage as zero
+// (buffer range check); a tap that leaves the image (row edge, top / bottom row,
+// neighbouring image) is zeroed at fragment time: each lane keeps a 9-bit validity
+// mask per M sub-tile (computed once per tile) and an invalid lane reads a zero
+// row (the image's padding) instead — one select on the LDS address, no branch.
+// The weights stream through a ring of NS slots, NS - 1 k-tiles ahead, with ONE
+// barrier per k-tile: slice st + NS - 1 is issued right after step st's barrier,
+// into the slot step st - 1 read.  k-tiles (tap-major, 64 channels each) and their
+// two k = 32 halves run in conv_igemm_kernel's order on the same MFMA, so every
+// output element's fp32 accumulation sequence — and the output — is bit-identical.
+// Two blocks per CU: one block's halo fetch and epilogue run under the other's
+// MFMAs.  The epilogue stage aliases the halo.
+//
+// halo_swz: each 16-lane group of a ds_read_b128 fragment read covers rows
+// {0-3, 12-15} at chunk c and rows {4-11} at chunk c ^ 1 (or the reverse) of 16
+// consecutive rows: per row parity that is four consecutive row pairs with one
+// chunk and four with the other, so the pair index mod 4, XORed into chunk bits
+// 2:1, gives 16 distinct 16-B slots at ANY row shift (swz_chunk's 8-value key is
+// conflict-free only for 16-aligned fragments: 24 % conflict cycles on the shifted
+// reads, profiles/conv3x3_narrow.md).
+__device__ __forceinline__ int halo_swz(int row) { return ((row >> 1) & 3) << 1; }
+
+template <int WM, int WN, int TM, int TN, int NS, unsigned EPI>
+__global__ __launch_bounds__(64 * WM * WN, 2) void conv_halo_kernel(const bf16_t* __restrict__ T,
+                                                                    const bf16_t* __restrict__ B,
+                                                                    bf16_t* __restrict__ D, float* __restrict__ stats,
+                                                                    BnBwd bnb, Geo g, int HRP) {
+  constexpr int NW = WM * WN, RPP = 8 * NW;
+  constexpr int BM = WM * TM * 16, BN = WN * TN * 16, BR = BN / RPP;
+  static_assert(NW == 4 && (BR == 2 || BR == 4), "halo kernel: 4 waves, 64- or 128-wide N tiles");
+  extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
+  const int CH = g.C / BK;       // 64-channel sub-images (1 or 2)
+  const int HW1 = g.W + 1;
+  const int HR = BM + 2 * HW1;   // staged rows (HRP > HR: padded to whole rounds of 4 x 8-row DMA pieces)
+  char* halo = reinterpret_cast<char*>(smem);  // [CH][HRP][128 B]; rows HR.. stage as zeros
+  bf16_t* Bs = reinterpret_cast<bf16_t*>(halo + CH * HRP * 128);  // [NS][BN][BK]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave % WM, wn = wave / WM;
+  const int ntn = (g.N + BN - 1) / BN;
+  const int ntiles = ((g.M + BM - 1) / BM) * ntn;
+  // persistent blocks over XCD-local tile ranges (as conv_igemm_kernel)
+  const int nwg = gridDim.x;
+  const int G = nwg < 8 ? nwg : 8;
+  const int xcd = blockIdx.x % G, slot = blockIdx.x / G;
+  const int nslot = (nwg - xcd + G - 1) / G;
+  const int t_lo = (int)((long)ntiles * xcd / G), t_hi = (int)((long)ntiles * (xcd + 1) / G);
+  const int my_tiles = t_hi - t_lo > slot ? (t_hi - t_lo - slot + nslot - 1) / nslot : 0;
+  auto tile_of = [&](int i) { return t_lo + slot + i * nslot; };
+  if (my_tiles == 0) return;
+
+  const int kc = tid & 7, rbase = tid >> 3;
+  const int l8 = lane >> 3, pos = lane & 7;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int PQ = g.P * g.Q;
+  const float rPQ = 1.f / (float)PQ, rQ = 1.f / (float)g.Q;
+  const __amdgpu_buffer_rsrc_t rT = rsrc(T, g.t_bytes), rB = rsrc(B, g.b_bytes), rD = rsrc(D, g.d_bytes);
+  const __amdgpu_buffer_rsrc_t rBX = rsrc(bnb.x ? bnb.x : D, bnb.x ? g.d_bytes : 0u);
+  const __amdgpu_buffer_rsrc_t rBY = rsrc(bnb.y ? bnb.y : D, bnb.y ? g.d_bytes : 0u);
+  const EpiRes er{rD, rsrc(D, 0u), rBX, rBY};
+  const int nk = 9 * CH;
+  const int total = my_tiles * nk;
+
+  // weight ring: slice (tile, k-tile) -> slot, carried incrementally in issue order
+  unsigned b_off[BR];
+  int setup_tile = -1, nx_ti = 0, nx_kt = 0;
+  auto issue_b = [&](int buf) {
+    if (nx_ti != setup_tile) {
+      const int n0 = (tile_of(nx_ti) % ntn) * BN;
+#pragma unroll
+      for (int i = 0; i < BR; i++) {
+        const int n = n0 + rbase + RPP * i;
+        const int cs = (kc ^ swz_chunk(i * RPP + rbase)) * 8;
+        b_off[i] = n < g.N ? (unsigned)(n * g.K + cs) * 2u : kOOB;
+      }
+      setup_tile = nx_ti;
+    }
+#pragma unroll
+    for (int i = 0; i < BR; i++)
+      buf_dma16(rB, Bs + buf * BN * BK + (i * RPP + wave * 8) * BK, (int)b_off[i], nx_kt * BK * 2);
+    if (++nx_kt == nk) { nx_kt = 0; nx_ti++; }
+  };
+
+  // halo of one tile: 1-KiB pieces (8 rows x 128 B) dealt round-robin to the waves,
+  // CH * HRP / 32 per wave (the same count on every wave: counted vmcnt waits);
+  // and this lane's tap-validity masks, one per M sub-tile
+  unsigned amask[TM];
+  const int npw = CH * HRP / 32;
+  auto stage = [&](int tile) {
+    const int m0 = (tile / ntn) * BM;
+    for (int jj = 0; jj < npw; jj++) {
+      const int j = jj * 4 + wave;
+      const int h = j * 8 >= HRP ? 1 : 0;
+      const int row = j * 8 - h * HRP + l8;
+      const int pix = m0 - HW1 + row;
+      const bool ok = row < HR && (unsigned)pix < (unsigned)g.M;
+      const int vo = ok ? (pix * g.C + h * BK + ((pos ^ halo_swz(row)) << 3)) * 2 : (int)kOOB;
+      buf_dma16<KFA_CONV_LOAD_AUX>(rT, halo + j * 1024, vo, 0);
+    }
+#pragma unroll
+    for (int mi = 0; mi < TM; mi++) {
+      const int m = m0 + wm * TM * 16 + mi * 16 + fr;
+      const int nb = fdiv(m, PQ, rPQ), rem = m - nb * PQ;
+      const int p = fdiv(rem, g.Q, rQ), q = rem - p * g.Q;
+      unsigned mk = 0;
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int s = 0; s < 3; s++) {
+          const bool ok = (unsigned)(p + r * g.ra + g.oa) < (unsigned)g.H && (unsigned)(q + s * g.ra + g.ob) < (unsigned)g.W;
+          mk |= ok ? 1u << (r * 3 + s) : 0u;
+        }
+      amask[mi] = mk;
+    }
+  };
+
+  floatx4 acc[TN][TM];
+#pragma unroll
+  for (int i = 0; i < TN; i++)
+#pragma unroll
+    for (int j = 0; j < TM; j++) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+
+  const unsigned halo_la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)halo;
+  const unsigned zero_la = halo_la + (unsigned)(((CH - 1) * HRP + HR) * 128 + fq * 16);  // padding row, restaged per tile
+  int c_r = 0, c_s = 0, c_h = 0;  // the k-tile compute() runs next: tap (c_r, c_s), sub-image c_h
+  // fragment reads ahead of the MFMAs, counted lgkmcnt, as conv_igemm_kernel's 4-wave form
+  auto compute = [&](int buf) {
+    const bf16_t* Bb = Bs + buf * BN * BK;
+    const int row0 = wm * TM * 16 + fr + HW1 + (c_r * g.ra + g.oa) * g.W + (c_s * g.ra + g.ob);
+    const int x = halo_swz(row0);  // rows row0 + 16 mi share it
+    const unsigned base = halo_la + (unsigned)((c_h * HRP + row0) * 128);
+    const unsigned a0 = base + (unsigned)((fq ^ x) << 4), a1 = base + (unsigned)(((4 + fq) ^ x) << 4);
+    const unsigned bit = 1u << (c_r * 3 + c_s);
+    if (++c_h == CH) {
+      c_h = 0;
+      if (++c_s == 3) { c_s = 0; if (++c_r == 3) c_r = 0; }
+    }
+    short8 af[2][TM], bf[2][TN];
+    auto mfma = [&](int ks) {
+#pragma unroll
+      for (int ni = 0; ni < TN; ni++)
+#pragma unroll
+        for (int mi = 0; mi < TM; mi++)
+          acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[ks][ni], af[ks][mi], acc[ni][mi], 0, 0, 0);
+    };
+    auto rda = [&](unsigned la) {
+      short8 v;
+      asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(la) : "memory");
+      return v;
+    };
+    auto rd = [&](const bf16_t* p) { return rda((unsigned)(uintptr_t)(__attribute__((address_space(3))) const bf16_t*)p); };
+#pragma unroll
+    for (int i = 0; i < TN; i++) bf[0][i] = rd(Bb + swz128(wn * TN * 16 + i * 16 + fr, fq));
+#pragma unroll
+    for (int i = 0; i < TM; i++) af[0][i] = rda((amask[i] & bit) ? a0 + i * 2048 : zero_la);
+#pragma unroll
+    for (int i = 0; i < TN; i++) bf[1][i] = rd(Bb + swz128(wn * TN * 16 + i * 16 + fr, 4 + fq));
+    lgkm_wait<TN>();
+    __builtin_amdgcn_sched_barrier(0);
+    mfma(0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < TM; i++) af[1][i] = rda((amask[i] & bit) ? a1 + i * 2048 : zero_la);
+    lgkm_wait<0>();
+    __builtin_amdgcn_sched_barrier(0);
+    mfma(1);
+  };
+  constexpr int WT = 256 * TM * TN;  // staged elements per wave (one pass)
+  auto epilogue = [&](int tile) {
+    const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
+    conv_epilogue<TM, TN, 1, EPI>(g, acc, halo + wave * WT * 2, true, lane, m0 + wm * TM * 16, n0 + wn * TN * 16, PQ,
+                                  rPQ, rQ, true, nullptr, stats, bnb, er);
+  };
+
+  stage(tile_of(0));
+#pragma unroll
+  for (int i = 0; i < NS - 1; i++)
+    if (i < total) issue_b(i);
+  int kt = 0, ti = 0, buf = 0, nbuf = NS - 1;
+  for (int st = 0; st < total; st++) {
+    // slice st landed — and, at a tile's first step, its halo (nothing younger is in flight
+    // then: the slices ahead were issued before it); up to NS - 2 slices ahead stay in flight
+    if (kt == 0 || NS == 2 || st + 1 >= total) vm_wait<0>();
+    else vm_wait<(NS - 2) * BR>();
+    asm volatile("s_barrier" ::: "memory");  // ... for every wave, which is also done reading slot `nbuf` (step st-1)
+    if (st + NS - 1 < total) issue_b(nbuf);
+    compute(buf);
+    buf = buf + 1 == NS ? 0 : buf + 1;
+    nbuf = nbuf + 1 == NS ? 0 : nbuf + 1;
+    if (++kt == nk) {
+      kt = 0;
+      epilogue(tile_of(ti));  // its first barrier: every wave is done reading the halo
+      lds_barrier();          // the stage is read back: the next halo may land on it
+      if (++ti < my_tiles) stage(tile_of(ti));
+    }
+  }
+}
+
 // zero-fill D rows of the output pixel mapping that the GEMM does not cover
 __global__ void zero_bf16(bf16_t* __restrict__ p, long n8) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x)
@@ -1050,6 +1257,30 @@ static void launch_igemm_pro(unsigned epi, dim3 grid, dim3 block, int lds, hipSt
 #undef KFA_IGP
 }
 
+// halo-staged 3x3 launches (no addend): EPI 0, forward statistics, backward statistics
+template <int WM, int WN, int TM, int TN, int NS>
+static void launch_halo(unsigned epi, dim3 grid, int lds, hipStream_t st, const bf16_t* T, const bf16_t* B, bf16_t* D,
+                        float* stats, const BnBwd& bnb, const Geo& g, int HRP) {
+#define KFA_HALO(EP)                                                                                            \
+  case EP: {                                                                                                    \
+    static int attr = 65536;                                                                                    \
+    if (lds > attr) {                                                                                           \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<WM, WN, TM, TN, NS, EP>),           \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);                               \
+      attr = lds;                                                                                               \
+    }                                                                                                           \
+    hipLaunchKernelGGL((conv_halo_kernel<WM, WN, TM, TN, NS, EP>), grid, dim3(256), lds, st, T, B, D, stats, bnb, g, \
+                       HRP);                                                                                    \
+  } break;
+  switch (pick_epi(epi)) {
+    KFA_HALO(0u)
+    KFA_HALO(kEpiStats)
+    default:  // backward statistics, mask from x / ss or the bit mask (no kEpiYMask: host-checked)
+      KFA_HALO(kEpiStats | kEpiBnBwd)
+  }
+#undef KFA_HALO
+}
+
 template <unsigned EP>
 static void launch_pp1(int wr, dim3 grid, hipStream_t st, const bf16_t* T, const bf16_t* B, bf16_t* D,
                        const bf16_t* E, float* stats, const BnBwd& bnb, const Geo& g) {
@@ -1077,7 +1308,9 @@ static void launch_pp(int wr, unsigned epi, dim3 grid, hipStream_t st, const bf1
 
 // variant: 0 = 128x128 tile, 1 = 128x64 tile (N <= 64), 2 = 256x256 tile (8 waves), 3 = 256x64 (N <= 64),
 // 4 = 256x256 ping-pong (conv_pp_kernel: C % 64 == 0, K > 0; one block per tile),
-// 6 = 512x128 ping-pong (conv_pp_kernel<.., 4>: the 128-channel layers, same conditions)
+// 6 = 512x128 ping-pong (conv_pp_kernel<.., 4>: the 128-channel layers, same conditions),
+// 7 = halo-staged (conv_halo_kernel: 3x3, stride 1, 'same' padding, C = 64 / 128, no addend,
+//     no ReLU mask read from bn_y; else -6)
 KFA_API int kfa_conv_igemm(const bf16_t* T, const bf16_t* B, bf16_t* D, const bf16_t* E, int Nb, int H, int W, int C,
                            int P, int Q, int R, int S, int sa, int ra, int oa, int ob, int N, int OH, int OW, int os,
                            int oph, int opw, int ldd, int variant, float* stats, const bf16_t* bn_x,
@@ -1120,6 +1353,20 @@ KFA_API int kfa_conv_igemm(const bf16_t* T, const bf16_t* B, bf16_t* D, const bf
   } else if (variant == 6 && C % BK == 0 && g.K > 0) {  // ping-pong 512 x 128
     launch_pp(4, epi, dim3((unsigned)((long)kfa_ceil_div(g.M, 512) * kfa_ceil_div(N, 128))), st, T, B, D, E, stats,
               bnb, g);
+  } else if (variant == 7) {  // halo-staged 3x3 (conv_halo_kernel): 256 x 64 tiles at C = 64, 128 x 128 at C = 128
+    const bool same3 = R == 3 && S == 3 && sa == 1 && (ra == 1 || ra == -1) && oa == -ra && ob == -ra && H == P &&
+                       W == Q && os == 1 && oph == 0 && opw == 0 && OH == P && OW == Q;
+    if (!same3 || E || (epi & kEpiYMask) || (C != 64 && C != 128)) return -6;
+    const int bm = C == 64 ? 256 : 128, bn = C == 64 ? 64 : 128;
+    const int hrp = (bm + 2 * (W + 1) + 1 + 31) & ~31;  // staged rows + a zero row, whole rounds of DMA pieces
+    const int ns = C == 64 ? 3 : 2;  // weight ring slots (8 KB / 16 KB each)
+    const int lds = (C / 64) * hrp * 128 + ns * bn * BK * 2;
+    if (lds > 160 * 1024) return -6;
+    const long tiles = (long)kfa_ceil_div(g.M, bm) * kfa_ceil_div(N, bn);
+    const long per_cu = lds <= 80 * 1024 ? 2 : 1;
+    const int grid = (int)(tiles < per_cu * cus ? tiles : per_cu * cus);
+    if (C == 64) launch_halo<4, 1, 4, 4, 3>(epi, dim3(grid), lds, st, T, B, D, stats, bnb, g, hrp);
+    else launch_halo<2, 2, 4, 4, 2>(epi, dim3(grid), lds, st, T, B, D, stats, bnb, g, hrp);
   } else if (variant == 3) {  // 256 x 64 tile (Cout <= 64): 4 waves of 64x64, 80 KB LDS -> 2 blocks / CU
     const int grid = pgrid((long)kfa_ceil_div(g.M, 256) * kfa_ceil_div(N, 64));
     launch_igemm<4, 1, 4, 4>(epi, dim3(grid), dim3(256), 2 * (256 + 64) * BK * 2, st, T, B, D, E, stats, bnb, g);

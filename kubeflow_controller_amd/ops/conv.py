@@ -171,6 +171,20 @@ _IG_VARIANT, _IG_STATS = 23, 24  # argument positions in kfa_conv_igemm
 _pp_scratch: dict = {}
 
 
+def _halo_ok(args: list) -> bool:
+    """``kfa_conv_igemm`` variant 7 covers this launch: 3x3, stride 1, 'same' padding (forward
+    or the stride-1 dgrad), 64 or 128 input channels, linear output, no addend, and no ReLU
+    mask read from the BatchNorm output."""
+    _, _, _, E, _, H, W, C, P_, Q_, R, S, sa, ra, oa, ob, _, OH, OW, os_, oph, opw = args[:22]
+    if not (E is None and args[26] is None and R == 3 and S == 3 and sa == 1 and ra in (1, -1)
+            and oa == -ra and ob == -ra and C in (64, 128) and (H, W) == (P_, Q_) == (OH, OW)
+            and (os_, oph, opw) == (1, 0, 0)):
+        return False
+    # the staged run of a tile (tile rows + 2 (W + 1), per 64 channels) and the weight ring fit the 160 KB of LDS
+    bm, ring = (256, 3 * 8192) if C == 64 else (128, 2 * 16384)
+    return (C // 64) * ((bm + 2 * (W + 1) + 32) & ~31) * 128 + ring <= 160 * 1024
+
+
 def _igemm(args: list, stats_t=None, kind: str = "conv") -> None:
     """One ``kfa_conv_igemm`` launch; with ``KFA_CONV_PP=auto`` the tile variant of this
     launch shape (geometry + epilogue features) is the routed one: the default tile vs
@@ -210,6 +224,8 @@ def _igemm(args: list, stats_t=None, kind: str = "conv") -> None:
         if narrow:  # narrow layers: the 128x64 and 256x64 tiles compete
             other = 3 if args[_IG_VARIANT] == 1 else 1
             cands.append(("igemm256x64" if other == 3 else "igemm128x64", run(other), other))
+        if _halo_ok(args):  # stride-1 3x3 at 64 / 128 channels: the halo-staged kernel (input staged once per tile)
+            cands.append(("halo", run(7), 7))
         i = routes.decide(kind, key, dev, [(n, f) for n, f, _ in cands])
         if i:
             args = list(args)
