@@ -27,6 +27,7 @@
 // each ds_read_b128 hit 16 distinct 16-B slots.  Operand roles are chosen so
 // each lane's 4 accumulator rows are 4 CONSECUTIVE output channels (8-B stores).
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "tile.h"
@@ -1198,112 +1199,65 @@ static const bf16_t* zero_page() {
   return z;
 }
 
-// smallest compiled epilogue configuration covering `need` (see conv_igemm_kernel's EPI)
-static unsigned pick_epi(unsigned need) {
-  static const unsigned have[] = {0u, kEpiStats, kEpiE, kEpiE | kEpiEmb, kEpiStats | kEpiBnBwd,
-                                  kEpiE | kEpiStats | kEpiBnBwd, kEpiE | kEpiEmb | kEpiStats | kEpiBnBwd};
-  for (unsigned h : have)
-    if ((need & ~h) == 0) return h;
-  return kEpiAll;
+// The epilogue sets a kernel family is compiled with (see conv_igemm_kernel's EPI), in the
+// order with_epi tries them.
+template <unsigned... EPI>
+struct EpiList {};
+using IgemmEpis = EpiList<0u, kEpiStats, kEpiE, kEpiE | kEpiEmb, kEpiStats | kEpiBnBwd, kEpiE | kEpiStats | kEpiBnBwd,
+                          kEpiE | kEpiEmb | kEpiStats | kEpiBnBwd, kEpiAll>;  // conv_igemm_kernel, conv_pp_kernel
+using ProEpis = EpiList<0u, kEpiStats>;  // PRO (forward convs reading a BatchNorm's raw input)
+// halo-staged 3x3 (no addend; no kEpiYMask: host-checked): forward statistics, backward statistics
+using HaloEpis = EpiList<0u, kEpiStats, kEpiStats | kEpiBnBwd>;
+
+// f(std::integral_constant<unsigned, EP>) for the first set EP of the list covering `need`
+// (the last one if none does); only the list's sets are instantiated
+template <class F, unsigned EP, unsigned... REST>
+static void with_epi(unsigned need, EpiList<EP, REST...>, F&& f) {
+  if (sizeof...(REST) == 0 || (need & ~EP) == 0) f(std::integral_constant<unsigned, EP>{});
+  else if constexpr (sizeof...(REST) > 0) with_epi(need, EpiList<REST...>{}, f);
 }
 
-template <int WM, int WN, int TM, int TN>
-static void launch_igemm(unsigned epi, dim3 grid, dim3 block, int lds, hipStream_t st, const bf16_t* T, const bf16_t* B,
-                         bf16_t* D, const bf16_t* E, float* stats, const BnBwd& bnb, const Geo& g) {
-#define KFA_IG(EP)                                                                                                   \
-  case EP:                                                                                                           \
-    if (lds > 65536) {                                                                                               \
-      static bool attr = false;                                                                                      \
-      if (!attr) {                                                                                                   \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<WM, WN, TM, TN, EP>),             \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);                                  \
-        attr = true;                                                                                                 \
-      }                                                                                                              \
-    }                                                                                                                \
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, EP>), grid, block, lds, st, T, B, D, E, zero_page(), stats, \
-                       bnb, g);                                                                                      \
-    break;
-  switch (pick_epi(epi)) {
-    KFA_IG(0u)
-    KFA_IG(kEpiStats)
-    KFA_IG(kEpiE)
-    KFA_IG(kEpiE | kEpiEmb)
-    KFA_IG(kEpiStats | kEpiBnBwd)
-    KFA_IG(kEpiE | kEpiStats | kEpiBnBwd)
-    KFA_IG(kEpiE | kEpiEmb | kEpiStats | kEpiBnBwd)
-    default:
-      KFA_IG(kEpiAll)
+// Launch KERNEL with `lds` bytes of dynamic LDS, first raising the kernel's limit to at least
+// that (beyond the 64 KB every kernel may use; running maximum per instantiation).
+template <auto KERNEL, class... Args>
+static void launch(dim3 grid, dim3 block, int lds, hipStream_t st, Args... args) {
+  static int limit = 65536;
+  if (lds > limit) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    limit = lds;
   }
-#undef KFA_IG
+  hipLaunchKernelGGL(KERNEL, grid, block, lds, st, args...);
 }
 
-// PRO launches (forward convs reading a BatchNorm's raw input): EPI 0 or stats only
-template <int WM, int WN, int TM, int TN>
-static void launch_igemm_pro(unsigned epi, dim3 grid, dim3 block, int lds, hipStream_t st, const bf16_t* T,
-                             const bf16_t* B, bf16_t* D, float* stats, const Geo& g, const Pro& pro) {
-  const BnBwd bnb{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
-#define KFA_IGP(EP)                                                                                                   \
-  {                                                                                                                   \
-    static bool attr = false;                                                                                         \
-    if (!attr && lds > 65536) {                                                                                       \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<WM, WN, TM, TN, EP, true>),          \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);                                     \
-      attr = true;                                                                                                    \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, EP, true>), grid, block, lds, st, T, B, D, nullptr,          \
-                       zero_page(), stats, bnb, g, pro);                                                              \
+// Block tiles of conv_igemm_kernel (variants 0-3): WM x WN waves of 16 TM x 16 TN each, double-
+// buffered operands in LDS, PER_CU resident blocks per CU (the persistent grid's cap);
+// OVERSUB: KFA_CONV_OVERSUB scales that cap (plain launches only).
+template <int WM_, int WN_, int TM_, int TN_, int PER_CU, bool OVERSUB>
+struct Tile {
+  static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_, per_cu = PER_CU;
+  static constexpr bool oversub = OVERSUB;
+  static constexpr int bm = WM * TM * 16, bn = WN * TN * 16, threads = 64 * WM * WN, lds = 2 * (bm + bn) * BK * 2;
+};
+
+template <class F>
+static void with_tile(int variant, F&& f) {
+  switch (variant) {
+    case 1: return f(Tile<4, 1, 2, 4, 3, false>{});  // 128 x 64 (Cout <= 64): 4 waves of 32x64, 48 KB LDS
+    case 2: return f(Tile<2, 4, 8, 4, 1, false>{});  // 256 x 256: 2x4 waves of 128x64, 128 KiB LDS
+    case 3: return f(Tile<4, 1, 4, 4, 2, true>{});   // 256 x 64 (Cout <= 64): 4 waves of 64x64, 80 KB LDS
+    default: return f(Tile<2, 2, 4, 4, 2, true>{});  // 128 x 128: 2x2 waves of 64x64, 64 KB LDS
   }
-  if (epi & kEpiStats) KFA_IGP(kEpiStats) else KFA_IGP(0u)
-#undef KFA_IGP
 }
 
-// halo-staged 3x3 launches (no addend): EPI 0, forward statistics, backward statistics
-template <int WM, int WN, int TM, int TN, int NS>
-static void launch_halo(unsigned epi, dim3 grid, int lds, hipStream_t st, const bf16_t* T, const bf16_t* B, bf16_t* D,
-                        float* stats, const BnBwd& bnb, const Geo& g, int HRP) {
-#define KFA_HALO(EP)                                                                                            \
-  case EP: {                                                                                                    \
-    static int attr = 65536;                                                                                    \
-    if (lds > attr) {                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<WM, WN, TM, TN, NS, EP>),           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);                               \
-      attr = lds;                                                                                               \
-    }                                                                                                           \
-    hipLaunchKernelGGL((conv_halo_kernel<WM, WN, TM, TN, NS, EP>), grid, dim3(256), lds, st, T, B, D, stats, bnb, g, \
-                       HRP);                                                                                    \
-  } break;
-  switch (pick_epi(epi)) {
-    KFA_HALO(0u)
-    KFA_HALO(kEpiStats)
-    default:  // backward statistics, mask from x / ss or the bit mask (no kEpiYMask: host-checked)
-      KFA_HALO(kEpiStats | kEpiBnBwd)
-  }
-#undef KFA_HALO
-}
+static int capped(long tiles, long slots) { return (int)(tiles < slots ? tiles : slots); }
 
-template <unsigned EP>
-static void launch_pp1(int wr, dim3 grid, hipStream_t st, const bf16_t* T, const bf16_t* B, bf16_t* D,
-                       const bf16_t* E, float* stats, const BnBwd& bnb, const Geo& g) {
-  if (wr == 4) hipLaunchKernelGGL((conv_pp_kernel<EP, 4>), grid, dim3(512), 0, st, T, B, D, E, stats, bnb, g);
-  else hipLaunchKernelGGL((conv_pp_kernel<EP, 2>), grid, dim3(512), 0, st, T, B, D, E, stats, bnb, g);
-}
-
-static void launch_pp(int wr, unsigned epi, dim3 grid, hipStream_t st, const bf16_t* T, const bf16_t* B,
-                      bf16_t* D, const bf16_t* E, float* stats, const BnBwd& bnb, const Geo& g) {
-  switch (pick_epi(epi)) {
-    case 0u: launch_pp1<0u>(wr, grid, st, T, B, D, E, stats, bnb, g); break;
-    case kEpiStats: launch_pp1<kEpiStats>(wr, grid, st, T, B, D, E, stats, bnb, g); break;
-    case kEpiE: launch_pp1<kEpiE>(wr, grid, st, T, B, D, E, stats, bnb, g); break;
-    case kEpiE | kEpiEmb: launch_pp1<kEpiE | kEpiEmb>(wr, grid, st, T, B, D, E, stats, bnb, g); break;
-    case kEpiStats | kEpiBnBwd: launch_pp1<kEpiStats | kEpiBnBwd>(wr, grid, st, T, B, D, E, stats, bnb, g); break;
-    case kEpiE | kEpiStats | kEpiBnBwd:
-      launch_pp1<kEpiE | kEpiStats | kEpiBnBwd>(wr, grid, st, T, B, D, E, stats, bnb, g);
-      break;
-    case kEpiE | kEpiEmb | kEpiStats | kEpiBnBwd:
-      launch_pp1<kEpiE | kEpiEmb | kEpiStats | kEpiBnBwd>(wr, grid, st, T, B, D, E, stats, bnb, g);
-      break;
-    default: launch_pp1<kEpiAll>(wr, grid, st, T, B, D, E, stats, bnb, g); break;
-  }
+// The Geo of one launch; false when a buffer does not fit the 32-bit buffer offsets.
+static bool make_geo(Geo& g, int Nb, int H, int W, int C, int P, int Q, int R, int S, int sa, int ra, int oa, int ob,
+                     int N, int OH, int OW, int os, int oph, int opw, int ldd) {
+  const long tb = (long)Nb * H * W * C * 2, bb = (long)N * R * S * C * 2, db = (long)Nb * OH * OW * ldd * 2;
+  g = Geo{Nb, H, W, C, P, Q, R, S, sa, ra, oa, ob, Nb * P * Q, N, R * S * C, OH, OW, os, oph, opw, ldd,
+          (unsigned)tb, (unsigned)bb, (unsigned)db};
+  return tb < (long)kOOB && bb < (long)kOOB && db < (long)kOOB;
 }
 
 // variant: 0 = 128x128 tile, 1 = 128x64 tile (N <= 64), 2 = 256x256 tile (8 waves), 3 = 256x64 (N <= 64),
@@ -1324,35 +1278,32 @@ KFA_API int kfa_conv_igemm(const bf16_t* T, const bf16_t* B, bf16_t* D, const bf
   const bool multi_tap = C % 8 == 0 && C < BK && BK % C == 0 && (S * C) % BK == 0 && sa == 1 && ra == 1 &&
                          oa == 0 && ob == 0;
   if ((C % BK != 0 && !multi_tap) || N % 8 != 0 || ldd % 8 != 0) return -1;
-  Geo g{Nb, H, W, C, P, Q, R, S, sa, ra, oa, ob, Nb * P * Q, N, R * S * C, OH, OW, os, oph, opw, ldd, 0, 0, 0};
+  Geo g;
+  if (!make_geo(g, Nb, H, W, C, P, Q, R, S, sa, ra, oa, ob, N, OH, OW, os, oph, opw, ldd)) return -2;
   if (g.K == 0) g.R = g.S = 1;  // keep index math defined; nk == 0 -> zero/addend-only epilogue
-  const long tb = (long)Nb * H * W * C * 2, bb = (long)N * R * S * C * 2, db = (long)Nb * OH * OW * ldd * 2;
-  if (tb >= (long)kOOB || bb >= (long)kOOB || db >= (long)kOOB) return -2;  // 32-bit buffer offsets
-  g.t_bytes = (unsigned)tb;
-  g.b_bytes = (unsigned)bb;
-  g.d_bytes = (unsigned)db;
   if (g.M <= 0) return 0;
   const int cus = kfa_cu_count();
-  // persistent grid: 2 resident blocks per CU (64 KB LDS, <=256 VGPR/2 waves).
-  // KFA_CONV_OVERSUB=k caps the grid at k x that (0: one block per tile), so the
-  // dispatcher, not the tile ranges, balances the work when other kernels (RCCL)
-  // hold part of the CUs.
+  // persistent grid: PER_CU resident blocks per CU.  KFA_CONV_OVERSUB=k caps the grid of the
+  // 2-per-CU tiles at k x that (0: one block per tile), so the dispatcher, not the tile
+  // ranges, balances the work when other kernels (RCCL) hold part of the CUs.
   static int oversub = -1;
   if (oversub < 0) {
     const char* e = getenv("KFA_CONV_OVERSUB");
     oversub = e ? atoi(e) : 1;
     if (oversub < 0) oversub = 1;
   }
-  const long slots = oversub == 0 ? (1L << 30) : 2L * cus * oversub;
-  auto pgrid = [&](long tiles) { return (int)(tiles < slots ? tiles : slots); };
   const unsigned epi = (E ? kEpiE : 0u) | (stats ? kEpiStats : 0u) | (bn_x ? kEpiBnBwd : 0u) |
                        ((E && add_mb) ? kEpiEmb : 0u) | ((bn_x && bn_y && bn_relu) ? kEpiYMask : 0u);
-  if (variant == 4 && C % BK == 0 && g.K > 0) {  // ping-pong 256 x 256 (grid = tiles, one block per CU resident)
-    launch_pp(2, epi, dim3((unsigned)((long)kfa_ceil_div(g.M, 256) * kfa_ceil_div(N, 256))), st, T, B, D, E, stats,
-              bnb, g);
-  } else if (variant == 6 && C % BK == 0 && g.K > 0) {  // ping-pong 512 x 128
-    launch_pp(4, epi, dim3((unsigned)((long)kfa_ceil_div(g.M, 512) * kfa_ceil_div(N, 128))), st, T, B, D, E, stats,
-              bnb, g);
+  auto tiles = [&](int bm, int bn) { return (long)kfa_ceil_div(g.M, bm) * kfa_ceil_div(N, bn); };
+  if ((variant == 4 || variant == 6) && C % BK == 0 && g.K > 0) {
+    // ping-pong 256 x 256 / 512 x 128 (grid = tiles, one block per CU resident)
+    const bool wide = variant == 6;
+    const dim3 grid((unsigned)(wide ? tiles(512, 128) : tiles(256, 256)));
+    with_epi(epi, IgemmEpis{}, [&](auto ep) {
+      constexpr unsigned EP = decltype(ep)::value;
+      if (wide) launch<conv_pp_kernel<EP, 4>>(grid, dim3(512), 0, st, T, B, D, E, stats, bnb, g);
+      else launch<conv_pp_kernel<EP, 2>>(grid, dim3(512), 0, st, T, B, D, E, stats, bnb, g);
+    });
   } else if (variant == 7) {  // halo-staged 3x3 (conv_halo_kernel): 256 x 64 tiles at C = 64, 128 x 128 at C = 128
     const bool same3 = R == 3 && S == 3 && sa == 1 && (ra == 1 || ra == -1) && oa == -ra && ob == -ra && H == P &&
                        W == Q && os == 1 && oph == 0 && opw == 0 && OH == P && OW == Q;
@@ -1362,25 +1313,22 @@ KFA_API int kfa_conv_igemm(const bf16_t* T, const bf16_t* B, bf16_t* D, const bf
     const int ns = C == 64 ? 3 : 2;  // weight ring slots (8 KB / 16 KB each)
     const int lds = (C / 64) * hrp * 128 + ns * bn * BK * 2;
     if (lds > 160 * 1024) return -6;
-    const long tiles = (long)kfa_ceil_div(g.M, bm) * kfa_ceil_div(N, bn);
-    const long per_cu = lds <= 80 * 1024 ? 2 : 1;
-    const int grid = (int)(tiles < per_cu * cus ? tiles : per_cu * cus);
-    if (C == 64) launch_halo<4, 1, 4, 4, 3>(epi, dim3(grid), lds, st, T, B, D, stats, bnb, g, hrp);
-    else launch_halo<2, 2, 4, 4, 2>(epi, dim3(grid), lds, st, T, B, D, stats, bnb, g, hrp);
-  } else if (variant == 3) {  // 256 x 64 tile (Cout <= 64): 4 waves of 64x64, 80 KB LDS -> 2 blocks / CU
-    const int grid = pgrid((long)kfa_ceil_div(g.M, 256) * kfa_ceil_div(N, 64));
-    launch_igemm<4, 1, 4, 4>(epi, dim3(grid), dim3(256), 2 * (256 + 64) * BK * 2, st, T, B, D, E, stats, bnb, g);
-  } else if (variant == 1) {  // 128 x 64 tile (Cout <= 64): 4 waves of 32x64
-    const long tiles = (long)kfa_ceil_div(g.M, 128) * kfa_ceil_div(N, 64);
-    const int grid = (int)(tiles < 3L * cus ? tiles : 3L * cus);  // 48 KB LDS: up to 3 blocks / CU
-    launch_igemm<4, 1, 2, 4>(epi, dim3(grid), dim3(256), 2 * (128 + 64) * BK * 2, st, T, B, D, E, stats, bnb, g);
-  } else if (variant == 2) {  // 256 x 256 tile: 2x4 waves of 128x64, one block per CU (128 KiB LDS)
-    const long tiles = (long)kfa_ceil_div(g.M, 256) * kfa_ceil_div(N, 256);
-    const int grid = (int)(tiles < cus ? tiles : cus);
-    launch_igemm<2, 4, 8, 4>(epi, dim3(grid), dim3(512), 2 * (256 + 256) * BK * 2, st, T, B, D, E, stats, bnb, g);
-  } else {  // 128 x 128 tile: 2x2 waves of 64x64
-    const int grid = pgrid((long)kfa_ceil_div(g.M, 128) * kfa_ceil_div(N, 128));
-    launch_igemm<2, 2, 4, 4>(epi, dim3(grid), dim3(256), 2 * (128 + 128) * BK * 2, st, T, B, D, E, stats, bnb, g);
+    const dim3 grid(capped(tiles(bm, bn), (lds <= 80 * 1024 ? 2L : 1L) * cus));
+    with_epi(epi, HaloEpis{}, [&](auto ep) {
+      constexpr unsigned EP = decltype(ep)::value;
+      if (C == 64) launch<conv_halo_kernel<4, 1, 4, 4, 3, EP>>(grid, dim3(256), lds, st, T, B, D, stats, bnb, g, hrp);
+      else launch<conv_halo_kernel<2, 2, 4, 4, 2, EP>>(grid, dim3(256), lds, st, T, B, D, stats, bnb, g, hrp);
+    });
+  } else {
+    with_tile(variant, [&](auto t) {
+      using TL = decltype(t);
+      const long slots = !TL::oversub ? (long)TL::per_cu * cus : oversub == 0 ? (1L << 30) : 2L * cus * oversub;
+      const dim3 grid(capped(tiles(TL::bm, TL::bn), slots));
+      with_epi(epi, IgemmEpis{}, [&](auto ep) {
+        launch<conv_igemm_kernel<TL::WM, TL::WN, TL::TM, TL::TN, decltype(ep)::value>>(
+            grid, dim3(TL::threads), TL::lds, st, T, B, D, E, zero_page(), stats, bnb, g, Pro{nullptr, nullptr});
+      });
+    });
   }
   return kfa_status();
 }
@@ -1395,31 +1343,21 @@ KFA_API int kfa_conv_igemm_bnpro(const bf16_t* T, const bf16_t* B, bf16_t* D, co
                                  int variant, float* stats, hipStream_t st) {
   if (!ss || C % BK != 0 || N % 8 != 0 || C > 2048) return -1;
   if (y && !(stride == 1 && P == H && Q == W && 2 * pad == R - 1 && 2 * pad == S - 1)) return -5;
-  Geo g{Nb, H, W, C, P, Q, R, S, stride, 1, -pad, -pad, Nb * P * Q, N, R * S * C, P, Q, 1, 0, 0, N, 0, 0, 0};
-  const long tb = (long)Nb * H * W * C * 2, bb = (long)N * R * S * C * 2, db = (long)Nb * P * Q * N * 2;
-  if (tb >= (long)kOOB || bb >= (long)kOOB || db >= (long)kOOB) return -2;
-  g.t_bytes = (unsigned)tb;
-  g.b_bytes = (unsigned)bb;
-  g.d_bytes = (unsigned)db;
+  Geo g;
+  if (!make_geo(g, Nb, H, W, C, P, Q, R, S, stride, 1, -pad, -pad, N, P, Q, 1, 0, 0, N)) return -2;
   if (g.M <= 0) return 0;
   const int cus = kfa_cu_count();
   const Pro pro{ss, y};
-  const unsigned epi = stats ? kEpiStats : 0u;
-  const int tab = 8 * C;  // the [scale | shift] table behind the operand ring
-  auto cap = [&](long tiles, long slots) { return (int)(tiles < slots ? tiles : slots); };
-  if (variant == 3) {
-    const int grid = cap((long)kfa_ceil_div(g.M, 256) * kfa_ceil_div(N, 64), 2L * cus);
-    launch_igemm_pro<4, 1, 4, 4>(epi, dim3(grid), dim3(256), 2 * (256 + 64) * BK * 2 + tab, st, T, B, D, stats, g, pro);
-  } else if (variant == 1) {
-    const int grid = cap((long)kfa_ceil_div(g.M, 128) * kfa_ceil_div(N, 64), 3L * cus);
-    launch_igemm_pro<4, 1, 2, 4>(epi, dim3(grid), dim3(256), 2 * (128 + 64) * BK * 2 + tab, st, T, B, D, stats, g, pro);
-  } else if (variant == 2) {
-    const int grid = cap((long)kfa_ceil_div(g.M, 256) * kfa_ceil_div(N, 256), cus);
-    launch_igemm_pro<2, 4, 8, 4>(epi, dim3(grid), dim3(512), 2 * (256 + 256) * BK * 2 + tab, st, T, B, D, stats, g, pro);
-  } else {
-    const int grid = cap((long)kfa_ceil_div(g.M, 128) * kfa_ceil_div(N, 128), 2L * cus);
-    launch_igemm_pro<2, 2, 4, 4>(epi, dim3(grid), dim3(256), 2 * (128 + 128) * BK * 2 + tab, st, T, B, D, stats, g, pro);
-  }
+  const BnBwd bnb{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
+  with_tile(variant, [&](auto t) {
+    using TL = decltype(t);
+    const dim3 grid(capped((long)kfa_ceil_div(g.M, TL::bm) * kfa_ceil_div(N, TL::bn), (long)TL::per_cu * cus));
+    const int lds = TL::lds + 8 * C;  // the [scale | shift] table behind the operand ring
+    with_epi(stats ? kEpiStats : 0u, ProEpis{}, [&](auto ep) {
+      launch<conv_igemm_kernel<TL::WM, TL::WN, TL::TM, TL::TN, decltype(ep)::value, true>>(
+          grid, dim3(TL::threads), lds, st, T, B, D, nullptr, zero_page(), stats, bnb, g, pro);
+    });
+  });
   return kfa_status();
 }
 

@@ -21,7 +21,9 @@ input on the same kernels (``csrc/kernels/stem.hip``, ``_StemConvFn``).
 """
 from __future__ import annotations
 
+import functools
 import math
+import operator
 import os
 import sys
 
@@ -33,7 +35,87 @@ from . import _lib
 from ..parallel.flat import direct_grad_view, notify_grad_ready
 
 P, I = _lib.P, _lib.I
-_lib.register("kfa_conv_igemm", [P, P, P, P] + [I] * 20 + [P, P, P, P, I, P, P, P, P])
+
+
+# kfa_conv_igemm's parameters under the prototype's names and in its order (* = pointer, the rest
+# int): the only place the order is written down
+_IGEMM_ABI = ("T* B* D* E* Nb H W C P Q R S sa ra oa ob N OH OW os oph opw ldd variant "
+              "stats* bn_x* bn_y* bn_mean* bn_relu bn_ss* bn_mb* add_mb* st*").split()
+_IGEMM_FIELDS = [f.rstrip("*") for f in _IGEMM_ABI]
+_IGEMM_GEOMETRY = _IGEMM_FIELDS[_IGEMM_FIELDS.index("Nb"):_IGEMM_FIELDS.index("variant")]  # a routing key's 19 ints
+_igemm_args, _igemm_geometry = operator.attrgetter(*_IGEMM_FIELDS), operator.attrgetter(*_IGEMM_GEOMETRY)
+
+
+class IgemmLaunch:
+    """One ``kfa_conv_igemm`` launch: a record with the fields of ``_IGEMM_ABI``, from which the
+    ctypes signature and the positional call are derived.  Every geometry int is required;
+    pointers default to null (``E``: the epilogue addend, ``stats``: the BatchNorm slot workspace,
+    ``add_mb``: ReLU bits masking ``E``), ``variant`` and ``bn_relu`` to 0.  The geometry builders
+    leave the pointers unset; ``replace`` attaches them."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(dict.fromkeys(f[:-1] for f in _IGEMM_ABI if f.endswith("*")), variant=0, bn_relu=0)
+        self.__dict__.update(fields)
+        if self.__dict__.keys() != set(_IGEMM_FIELDS):
+            raise TypeError(f"IgemmLaunch fields: {sorted(self.__dict__.keys() ^ set(_IGEMM_FIELDS))}")
+
+    def replace(self, **changes) -> "IgemmLaunch":
+        """A copy with some fields changed (the same launch on another variant, with pointers, ...)."""
+        if not changes.keys() <= self.__dict__.keys():
+            raise TypeError(f"IgemmLaunch has no field {sorted(changes.keys() - self.__dict__.keys())}")
+        new = object.__new__(IgemmLaunch)
+        new.__dict__.update(self.__dict__, **changes)
+        return new
+
+    @property
+    def M(self) -> int:
+        return self.Nb * self.P * self.Q
+
+    @property
+    def K(self) -> int:
+        return self.R * self.S * self.C
+
+    @property
+    def flags(self) -> tuple:
+        """Epilogue features of the routing key: addend, statistics, ``bn_x``, ``add_mb`` present."""
+        return tuple(int(p is not None) for p in (self.E, self.stats, self.bn_x, self.add_mb))
+
+    def route_key(self) -> tuple:
+        return _igemm_geometry(self) + self.flags
+
+    @property
+    def narrow(self) -> bool:
+        return self.N <= 64 and self.variant in (1, 3)
+
+    @property
+    def routed(self) -> bool:
+        """Routed: every launch with whole 64-channel k-slices; the narrow tiles also for the
+        multi-tap slices of the space-to-depth stem (C = 16), where only they apply."""
+        return self.N >= 64 and self.K > 0 and (self.C % 64 == 0 or self.narrow)
+
+    @property
+    def halo_ok(self) -> bool:
+        """Variant 7 covers this launch: 3x3, stride 1, 'same' padding (forward or the stride-1
+        dgrad), 64 or 128 input channels, linear output, no addend, and no ReLU mask read from
+        the BatchNorm output."""
+        if not (self.E is None and self.bn_y is None and self.R == 3 and self.S == 3 and self.sa == 1
+                and self.ra in (1, -1) and self.oa == -self.ra and self.ob == -self.ra and self.C in (64, 128)
+                and (self.H, self.W) == (self.P, self.Q) == (self.OH, self.OW)
+                and (self.os, self.oph, self.opw) == (1, 0, 0)):
+            return False
+        # the staged run of a tile (tile rows + 2 (W + 1), per 64 channels) and the weight ring fit the 160 KB of LDS
+        bm, ring = (256, 3 * 8192) if self.C == 64 else (128, 2 * 16384)
+        return (self.C // 64) * ((bm + 2 * (self.W + 1) + 32) & ~31) * 128 + ring <= 160 * 1024
+
+    def candidates(self) -> list:
+        """``(name, variant)`` of every tile variant competing for this launch, the default first."""
+        return [("igemm", self.variant)] + [(n, v) for n, (v, ok) in _CANDIDATES.items() if ok(self)]
+
+    def launch(self) -> None:
+        _lib.call("kfa_conv_igemm", *_igemm_args(self))
+
+
+_lib.register("kfa_conv_igemm", [P if f.endswith("*") else I for f in _IGEMM_ABI])
 _lib.register("kfa_conv_igemm_bnpro", [P] * 5 + [I] * 12 + [P, P])
 _lib.register("kfa_zero_bf16", [P, _lib.L, P])
 _lib.register("kfa_weight_transpose", [P, P] + [I] * 10 + [P])
@@ -108,13 +190,8 @@ def _agree(hit: bool, device) -> bool:
     the collective Engine): async-PS workers share their default group with PS
     tasks that never run the model, so a broadcast there would never complete —
     each async worker keeps its own decision."""
-    import torch.distributed as dist
-    if not _LOCKSTEP or not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-        return hit
-    from ..parallel.comm import control_device  # the CPU unless the default group is torch's RCCL
-    t = torch.tensor([1 if hit else 0], dtype=torch.int32, device=control_device(device))
-    dist.broadcast(t, 0)
-    return bool(t.item())
+    from . import routes
+    return bool(routes._agree_index(int(hit), device))
 
 
 def _use_vendor_fwd(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, stats) -> bool:
@@ -167,70 +244,44 @@ BIG_AUTO_E = os.environ.get("KFA_CONV_BIG_AUTO_E", "1") != "0"  # also for launc
 # 512x128 ping-pong tile (variant 6, the 128-channel layers) instead.
 PP = os.environ.get("KFA_CONV_PP", "auto")
 PP_MIN_N = int(os.environ.get("KFA_CONV_PP_MIN_N", "256"))
-_IG_VARIANT, _IG_STATS = 23, 24  # argument positions in kfa_conv_igemm
 _pp_scratch: dict = {}
 
+# Tile variants that compete with the default one (``_variant``'s static rule) for a routed
+# launch, in the order they are offered: name -> (``kfa_conv_igemm`` variant, eligibility of the
+# launch under its default variant).  Every ping-pong form competes, even with part of its tile
+# width empty: on the 64-channel 3x3s the 512x128 tile (half empty) still beats the 128x64 one
+# by 10 % (profiles/r5_conv_pp_layers.md).
+_CANDIDATES = {
+    "pp": (4, lambda a: a.C % 64 == 0),
+    "pp512": (6, lambda a: a.C % 64 == 0 and a.N <= 512),  # the 64 / 128-channel layers and narrow N <= 512 grids
+    "igemm128": (0, lambda a: a.variant == 2),  # the static rule chose the 8-wave 256x256 tile
+    "igemm128x64": (1, lambda a: a.narrow and a.variant == 3),  # narrow layers: the 128x64 and 256x64 tiles compete
+    "igemm256x64": (3, lambda a: a.narrow and a.variant == 1),
+    "halo": (7, lambda a: a.halo_ok),  # the halo-staged kernel (input staged once per tile)
+}
 
-def _halo_ok(args: list) -> bool:
-    """``kfa_conv_igemm`` variant 7 covers this launch: 3x3, stride 1, 'same' padding (forward
-    or the stride-1 dgrad), 64 or 128 input channels, linear output, no addend, and no ReLU
-    mask read from the BatchNorm output."""
-    _, _, _, E, _, H, W, C, P_, Q_, R, S, sa, ra, oa, ob, _, OH, OW, os_, oph, opw = args[:22]
-    if not (E is None and args[26] is None and R == 3 and S == 3 and sa == 1 and ra in (1, -1)
-            and oa == -ra and ob == -ra and C in (64, 128) and (H, W) == (P_, Q_) == (OH, OW)
-            and (os_, oph, opw) == (1, 0, 0)):
-        return False
-    # the staged run of a tile (tile rows + 2 (W + 1), per 64 channels) and the weight ring fit the 160 KB of LDS
-    bm, ring = (256, 3 * 8192) if C == 64 else (128, 2 * 16384)
-    return (C // 64) * ((bm + 2 * (W + 1) + 32) & ~31) * 128 + ring <= 160 * 1024
 
-
-def _igemm(args: list, stats_t=None, kind: str = "conv") -> None:
-    """One ``kfa_conv_igemm`` launch; with ``KFA_CONV_PP=auto`` the tile variant of this
-    launch shape (geometry + epilogue features) is the routed one: the default tile vs
-    the ping-pong kernel, from the table or timed once (statistics into a scratch
-    slot buffer, so the real BatchNorm slots only see the real launch)."""
-    N, K, C = args[16], args[10] * args[11] * args[7], args[7]
-    narrow = N <= 64 and args[_IG_VARIANT] in (1, 3)
-    # routed: every launch with whole 64-channel k-slices; the narrow tiles also for the
-    # multi-tap slices of the space-to-depth stem (C = 16), where only they apply
-    if PP == "auto" and N >= 64 and K > 0 and (C % 64 == 0 or narrow):
+def _igemm(geo: IgemmLaunch, kind: str, stats_t=None, **ptrs) -> None:
+    """One ``kfa_conv_igemm`` launch of ``geo`` with the pointers ``ptrs``; with
+    ``KFA_CONV_PP=auto`` the tile variant of this launch shape (geometry + epilogue features)
+    is the routed one: the default tile vs the other candidates, from the table or timed once
+    (statistics into a scratch slot buffer, so the real BatchNorm slots only see the real launch)."""
+    a = geo.replace(variant=_variant(geo.M, geo.N, geo.K, ptrs.get("E") is not None), st=_lib.stream(), **ptrs)
+    if PP == "auto" and a.routed:
         from . import routes
-        flags = tuple(int(args[i] is not None) for i in (3, _IG_STATS, 25, 31))
-        key = tuple(args[4:23]) + flags
         dev = stats_t.device if stats_t is not None else torch.device("cuda", torch.cuda.current_device())
-        sc = None
+        timed = a
         if stats_t is not None:
             sc = _pp_scratch.get((stats_t.numel(), dev))
             if sc is None:
                 sc = _pp_scratch[(stats_t.numel(), dev)] = torch.zeros_like(stats_t)
-
-        def run(v):
-            a = list(args)
-            a[_IG_VARIANT] = v
-            if sc is not None:
-                a[_IG_STATS] = _lib.ptr(sc)
-            return lambda: _lib.call("kfa_conv_igemm", *a)
-        # every ping-pong form competes, even with part of its tile width empty: on the
-        # 64-channel 3x3s the 512x128 tile (half empty) still beats the 128x64 one by 10 %
-        # (profiles/r5_conv_pp_layers.md)
-        cands = [("igemm", run(args[_IG_VARIANT]), args[_IG_VARIANT])]
-        if C % 64 == 0:
-            cands.append(("pp", run(4), 4))
-            if N <= 512:  # 512 x 128 ping-pong: the 64 / 128-channel layers and narrow N <= 512 grids
-                cands.append(("pp512", run(6), 6))
-        if args[_IG_VARIANT] == 2:  # the static rule chose the 8-wave 256x256 tile: the 128x128 one competes too
-            cands.append(("igemm128", run(0), 0))
-        if narrow:  # narrow layers: the 128x64 and 256x64 tiles compete
-            other = 3 if args[_IG_VARIANT] == 1 else 1
-            cands.append(("igemm256x64" if other == 3 else "igemm128x64", run(other), other))
-        if _halo_ok(args):  # stride-1 3x3 at 64 / 128 channels: the halo-staged kernel (input staged once per tile)
-            cands.append(("halo", run(7), 7))
-        i = routes.decide(kind, key, dev, [(n, f) for n, f, _ in cands])
+            timed = a.replace(stats=_lib.ptr(sc))
+        cands = a.candidates()
+        i = routes.decide(kind, a.route_key(), dev,
+                          [(n, lambda v=v: timed.replace(variant=v).launch()) for n, v in cands])
         if i:
-            args = list(args)
-            args[_IG_VARIANT] = cands[i][2]
-    _lib.call("kfa_conv_igemm", *args)
+            a = a.replace(variant=cands[i][1])
+    a.launch()
 
 
 def _variant(M: int, N: int, K: int = 0, addend: bool = False) -> int:
@@ -250,19 +301,55 @@ def _cl(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
 
 
+@functools.lru_cache(maxsize=None)
+def fwd_geometry(x_shape: tuple, w_shape: tuple, stride: int, pad: int) -> IgemmLaunch:
+    """The forward conv of ``x`` [Nb, C, H, W] by ``w`` [Cout, C, R, S] as an implicit GEMM
+    (no pointers, variant unset)."""
+    Nb, C, H, W = x_shape
+    Co, _, R, S = w_shape
+    Po = (H + 2 * pad - R) // stride + 1
+    Qo = (W + 2 * pad - S) // stride + 1
+    return IgemmLaunch(Nb=Nb, H=H, W=W, C=C, P=Po, Q=Qo, R=R, S=S, sa=stride, ra=1, oa=-pad, ob=-pad, N=Co,
+                       OH=Po, OW=Qo, os=1, oph=0, opw=0, ldd=Co)
+
+
+@functools.lru_cache(maxsize=None)
+def dgrad_geometries(dy_shape: tuple, w_shape: tuple, x_shape: tuple, stride: int, pad: int) -> tuple:
+    """The data gradient as implicit GEMMs over dY with flipped taps: one
+    ``(geometry, (r0, dr, Rs, s0, ds, Ss))`` per output parity class (one class at stride 1),
+    the second the weight slice ``_transposed_weight`` cuts for it.  For class (ph, pw) the rows
+    h = s*i + ph receive taps r with (ph + pad - r) % s == 0, from dY row i + (ph + pad - r)/s.
+    A class no tap reaches (1x1/s2: 3 of 4) has K = 0: the kernel writes zeros (or the addend)
+    through the same strided output mapping."""
+    Nb, Co, Po, Qo = dy_shape
+    _, Ci, R, S = w_shape
+    H, W = x_shape[2], x_shape[3]
+    out = []
+    for ph in range(stride):
+        r0 = (ph + pad) % stride
+        Rs = len(range(r0, R, stride))
+        Hc = len(range(ph, H, stride))
+        for pw in range(stride):
+            s0 = (pw + pad) % stride
+            Ss = len(range(s0, S, stride))
+            Wc = len(range(pw, W, stride))
+            if Hc == 0 or Wc == 0:
+                continue
+            g = IgemmLaunch(Nb=Nb, H=Po, W=Qo, C=Co, P=Hc, Q=Wc, R=Rs, S=Ss, sa=1, ra=-1,
+                            oa=(ph + pad - r0) // stride, ob=(pw + pad - s0) // stride, N=Ci, OH=H, OW=W,
+                            os=stride, oph=ph, opw=pw, ldd=Ci)
+            out.append((g, (r0, stride, Rs, s0, stride, Ss)))
+    return tuple(out)
+
+
 def conv_fwd(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, stats=None) -> torch.Tensor:
     """Forward conv; with ``stats`` (the BatchNorm slot workspace of Cout) the
     epilogue also accumulates the per-channel sum / sum of squares of the output
     for the BatchNorm that consumes it (``kfa_bn_fwd_train_prestats``)."""
     x, w = _cl(x), _cl(w)
-    Nb, C, H, W = x.shape
-    Co, _, R, S = w.shape
-    Po = (H + 2 * pad - R) // stride + 1
-    Qo = (W + 2 * pad - S) // stride + 1
-    y = torch.empty((Nb, Co, Po, Qo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    _igemm([_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), None, Nb, H, W, C, Po, Qo, R, S, stride, 1,
-            -pad, -pad, Co, Po, Qo, 1, 0, 0, Co, _variant(Nb * Po * Qo, Co, R * S * C), _lib.ptr(stats), None, None,
-            None, 0, None, None, None, _lib.stream()], stats, "conv_fwd")
+    g = fwd_geometry(tuple(x.shape), tuple(w.shape), stride, pad)
+    y = torch.empty((g.Nb, g.N, g.P, g.Q), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    _igemm(g, "conv_fwd", stats, T=_lib.ptr(x), B=_lib.ptr(w), D=_lib.ptr(y), stats=_lib.ptr(stats))
     return y
 
 
@@ -281,15 +368,12 @@ def conv_fwd_bnpro(x: torch.Tensor, ss: torch.Tensor, w: torch.Tensor, stride: i
     implicit GEMM's A-operand load (``kfa_conv_igemm_bnpro``).  ``y_out`` (same
     shape as ``x``) receives the normalised activation for the weight gradient."""
     x, w = _cl(x), _cl(w)
-    Nb, C, H, W = x.shape
-    Co, _, R, S = w.shape
-    Po = (H + 2 * pad - R) // stride + 1
-    Qo = (W + 2 * pad - S) // stride + 1
-    y = torch.empty((Nb, Co, Po, Qo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    g = fwd_geometry(tuple(x.shape), tuple(w.shape), stride, pad)
+    y = torch.empty((g.Nb, g.N, g.P, g.Q), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     if y_out is not None and not y_out.is_contiguous(memory_format=torch.channels_last):
         raise ValueError("conv_fwd_bnpro: y_out must be channels-last")
-    _lib.call("kfa_conv_igemm_bnpro", _lib.ptr(x), _lib.ptr(w), _lib.ptr(y), _lib.ptr(ss), _lib.ptr(y_out), Nb, H, W,
-              C, Po, Qo, R, S, stride, pad, Co, _variant(Nb * Po * Qo, Co, R * S * C), _lib.ptr(stats), _lib.stream())
+    _lib.call("kfa_conv_igemm_bnpro", _lib.ptr(x), _lib.ptr(w), _lib.ptr(y), _lib.ptr(ss), _lib.ptr(y_out), g.Nb, g.H,
+              g.W, g.C, g.P, g.Q, g.R, g.S, stride, pad, g.N, _variant(g.M, g.N, g.K), _lib.ptr(stats), _lib.stream())
     return y
 
 
@@ -379,42 +463,17 @@ def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, x_shape, stride: int, pad: int
     EM = None if E is None else addend_mask
     if EM is not None and (EM.dtype != torch.uint8 or EM.numel() * 8 != dx.numel()):
         raise ValueError(f"conv_dgrad: addend mask of {EM.numel()} bytes for {dx.numel()} elements")
-    st = _lib.stream()
-    bn_args = (None, None, None, None, 0, None, None)
-    bn_ws = None
+    bn_args, bn_ws = {}, None
     if bn is not None:
         from .batchnorm import bn_slot_workspace
         bn_ws = bn_slot_workspace(Ci, dy.device)
-        bn_args = (_lib.ptr(bn_ws), _lib.ptr(bn.x), _lib.ptr(bn.y), _lib.ptr(bn.mean),
-                   int(bn.relu), _lib.ptr(bn.ss), _lib.ptr(bn.mb))
+        bn_args = dict(stats=_lib.ptr(bn_ws), bn_x=_lib.ptr(bn.x), bn_y=_lib.ptr(bn.y), bn_mean=_lib.ptr(bn.mean),
+                       bn_relu=int(bn.relu), bn_ss=_lib.ptr(bn.ss), bn_mb=_lib.ptr(bn.mb))
         bn.prestats = True
-    if stride == 1:
-        wt = _transposed_weight(w, 0, 1, R, 0, 1, S)
-        _igemm([_lib.ptr(dy), _lib.ptr(wt), _lib.ptr(dx), _lib.ptr(E), Nb, Po, Qo, Co, H, W, R, S,
-                1, -1, pad, pad, Ci, H, W, 1, 0, 0, Ci, _variant(Nb * H * W, Ci, R * S * Co, E is not None), *bn_args,
-                _lib.ptr(EM), st], bn_ws, "conv_dgrad")
-        return dx
-    # stride s: output parity classes.  For class (ph, pw) the rows h = s*i + ph
-    # receive taps r with (ph + pad - r) % s == 0, from dY row i + (ph + pad - r)/s.
-    for ph in range(stride):
-        r0 = (ph + pad) % stride
-        Rs = len(range(r0, R, stride))
-        Hc = len(range(ph, H, stride))
-        for pw in range(stride):
-            s0 = (pw + pad) % stride
-            Ss = len(range(s0, S, stride))
-            Wc = len(range(pw, W, stride))
-            if Hc == 0 or Wc == 0:
-                continue
-            # a class no tap reaches (1x1/s2: 3 of 4) runs with K = 0: the kernel
-            # writes zeros (or the addend) through the same strided output mapping
-            wt = _transposed_weight(w, r0, stride, Rs, s0, stride, Ss) if Rs * Ss else w
-            oa_h = (ph + pad - r0) // stride
-            oa_w = (pw + pad - s0) // stride
-            _igemm([_lib.ptr(dy), _lib.ptr(wt), _lib.ptr(dx), _lib.ptr(E), Nb, Po, Qo, Co, Hc, Wc,
-                    Rs, Ss, 1, -1, oa_h, oa_w, Ci, H, W, stride, ph, pw, Ci,
-                    _variant(Nb * Hc * Wc, Ci, Rs * Ss * Co, E is not None),
-                    *bn_args, _lib.ptr(EM), st], bn_ws, "conv_dgrad")
+    for g, taps in dgrad_geometries(tuple(dy.shape), tuple(w.shape), tuple(x_shape), stride, pad):
+        wt = _transposed_weight(w, *taps) if g.K else w
+        _igemm(g, "conv_dgrad", bn_ws, T=_lib.ptr(dy), B=_lib.ptr(wt), D=_lib.ptr(dx), E=_lib.ptr(E),
+               add_mb=_lib.ptr(EM), **bn_args)
     return dx
 
 
@@ -729,46 +788,38 @@ def conv2d(x, w, stride: int = 1, pad: int = 0, join: "GradJoin | None" = None, 
     for a BN whose finalize runs later than the next BN's (the downsample BN of
     ``bn_act_dual``); True = the shared one."""
     tag = bn_stats if isinstance(bn_stats, str) else "bn_slots"
+
+    def slots():  # the BN's slot workspace (fetched only on a path whose epilogue fills it)
+        if not bn_stats:
+            return None
+        from .batchnorm import bn_slot_workspace
+        return bn_slot_workspace(w.shape[0], x.device, tag)
+
+    def tagged(y, stats):
+        if stats is not None:
+            y._kfa_prestats = True
+            y._kfa_prestats_tag = tag
+        return y
+
     lz = getattr(x, "_kfa_lazy", None)
     if lz is not None and lz.pending and join is None and igemm_ok(x, w):
-        stats = None
-        if bn_stats:
-            from .batchnorm import bn_slot_workspace
-            stats = bn_slot_workspace(w.shape[0], x.device, tag)
+        stats = slots()
         if _use_bnpro(lz, x, w, stride, pad, stats):
-            y = _ConvFn.apply(x, w, stride, pad, None, stats, False, lz)
-            if stats is not None:
-                y._kfa_prestats = True
-                y._kfa_prestats_tag = tag
-            return y
+            return tagged(_ConvFn.apply(x, w, stride, pad, None, stats, False, lz), stats)
     if lz is not None and lz.pending:
         from .batchnorm import materialize
         materialize(x)
     if stem_ok(x, w, stride, pad) and join is None:
-        stats = None
-        if bn_stats:
-            from .batchnorm import bn_slot_workspace
-            stats = bn_slot_workspace(w.shape[0], x.device, tag)
-        y = _StemConvFn.apply(x, w, stride, pad, stats)
-        if stats is not None:
-            y._kfa_prestats = True
-            y._kfa_prestats_tag = tag
-        return y
+        stats = slots()
+        return tagged(_StemConvFn.apply(x, w, stride, pad, stats), stats)
     if igemm_ok(x, w):
         if join is not None:
             join.fused = True
-        stats = None
-        if bn_stats:
-            from .batchnorm import bn_slot_workspace
-            stats = bn_slot_workspace(w.shape[0], x.device, tag)
+        stats = slots()
         vendor = _use_vendor_fwd(x, w, stride, pad, stats)
         if vendor:
             stats = None  # the BN runs its own statistics pass
-        y = _ConvFn.apply(x, w, stride, pad, join, stats, vendor)
-        if stats is not None:
-            y._kfa_prestats = True
-            y._kfa_prestats_tag = tag
-        return y
+        return tagged(_ConvFn.apply(x, w, stride, pad, join, stats, vendor), stats)
     return F.conv2d(x, w, None, stride, pad)  # unfused: join.branch() is a no-op alias
 
 

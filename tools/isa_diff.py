@@ -25,6 +25,9 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 META = ["vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count",
         "group_segment_fixed_size", "private_segment_fixed_size"]
 DROP = re.compile(r"^\s*\.(file|ident)\b|__hip_cuid_|^\s*;.*\.(hip|h|cpp|hpp)\b")
+# local labels carry the function's index in the file (.LBB22_3, .Lfunc_end22): the order the
+# host code instantiates the kernels in, not device code
+LABEL = re.compile(r"(?<![\w.])(\.LBB|BB|\.Lfunc_begin|\.Lfunc_end)\d+")
 
 
 def hipcc():
@@ -58,11 +61,13 @@ def kernels(path):
     chunks, name = {}, None
     for line in body.splitlines():
         m = re.match(r"\s*\.type\s+(\S+),@function", line)
+        if re.match(r"\s*\.section\s+\.text", line):  # the next function's preamble
+            name = None
         if m:
             name = m.group(1)
             chunks[name] = []
         if name and not DROP.search(line):
-            chunks[name].append(line.rstrip())
+            chunks[name].append(LABEL.sub(r"\1", line.rstrip()))
     info = {}
     for entry in re.split(r"^  - ", meta, flags=re.M)[1:]:
         keys = dict(re.findall(r"^(?:    )?\.(\w+):\s+(.*)$", entry, flags=re.M))
