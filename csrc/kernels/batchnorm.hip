@@ -810,6 +810,48 @@ KFA_API int kfa_bn_bwd(const bf16_t* dy, const bf16_t* x, const bf16_t* y, const
   return kfa_status();
 }
 
+// Backward without the apply pass: statistics (from `slots` when prestats, else by the
+// partial pass) finalized into a caller-owned `coef` ([3][C] = a, b, k) plus dgamma / dbeta
+// as kfa_bn_bwd.  dx = a*dz + b*x + k is left to the consumer: the fused conv3 backward
+// (conv3_bwd.hip) forms it per tile, or kfa_bn_bwd_apply_only writes it.
+KFA_API int kfa_bn_bwd_finalize_only(const bf16_t* dy, const bf16_t* x, const bf16_t* y, const float* gamma,
+                                     const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
+                                     float* slots, float* coef, long M, int C, int relu, int accumulate,
+                                     const float* ss, const uint8_t* mb, int prestats, hipStream_t s) {
+  if (!bn_shape_ok(M, C) || !coef) return -1;
+  const int mm = mask_mode(relu, y, mb, ss);
+  if (mm < 0) return -2;
+  Geom g = geom(M, C, max_row_blocks(C));
+  if (!prestats) {
+    if (mm == 3)
+      hipLaunchKernelGGL(bn_bwd_partial<3>, dim3(g.gx), dim3(NT), 0, s, dy, x, y, mb, ss, save_mean, slots, M, C,
+                         g.chunk, g.tpr, g.rpi);
+    else if (mm == 2)
+      hipLaunchKernelGGL(bn_bwd_partial<2>, dim3(g.gx), dim3(NT), 0, s, dy, x, y, mb, ss, save_mean, slots, M, C,
+                         g.chunk, g.tpr, g.rpi);
+    else if (mm == 1)
+      hipLaunchKernelGGL(bn_bwd_partial<1>, dim3(g.gx), dim3(NT), 0, s, dy, x, y, mb, ss, save_mean, slots, M, C,
+                         g.chunk, g.tpr, g.rpi);
+    else
+      hipLaunchKernelGGL(bn_bwd_partial<0>, dim3(g.gx), dim3(NT), 0, s, dy, x, y, mb, ss, save_mean, slots, M, C,
+                         g.chunk, g.tpr, g.rpi);
+  }
+  hipLaunchKernelGGL(bn_bwd_finalize, dim3(kfa_ceil_div(C, 64)), dim3(64, kGroups), 0, s, slots, g.gx, M, C, gamma,
+                     save_mean, save_invstd, dgamma, dbeta, coef, accumulate);
+  return kfa_status();
+}
+
+// The apply pass alone, with the coefficients kfa_bn_bwd_finalize_only left in `coef`.
+KFA_API int kfa_bn_bwd_apply_only(const bf16_t* dy, const bf16_t* x, const bf16_t* y, const float* coef, bf16_t* dx,
+                                  long M, int C, int relu, const float* ss, const uint8_t* mb, hipStream_t s) {
+  if (!bn_shape_ok(M, C) || !coef) return -1;
+  const int mm = mask_mode(relu, y, mb, ss);
+  if (mm < 0) return -2;
+  Geom g = geom(M, C, max_row_blocks(C));
+  launch_bwd_apply_any(mm, g, dy, x, y, mb, ss, coef, dx, nullptr, M, C, s);
+  return kfa_status();
+}
+
 // ---------------------------------------------------------------- downsample-block pair
 // A ResNet downsample block ends in relu(bn3(x) + bn_ds(r)): r (the downsample
 // conv's output) is normalised inside bn3's apply pass (bn_apply RAFF) instead

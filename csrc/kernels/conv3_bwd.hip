@@ -1,0 +1,366 @@
+// One-pass backward of a bottleneck tail: bn3's backward apply + conv3's data and
+// weight gradients, for identity blocks whose conv3 is a 1x1 / stride-1 conv with
+// Ci = 64 or 128 input and Co = 4 Ci output channels (ResNet-50 stages 1 and 2).
+//
+// The separate path runs three passes over the [K, Co] tensors (K = Nb*P*Q pixels):
+//   bn_bwd_apply   reads g, x3 (+ ReLU bits)  writes dx3
+//   conv3 dgrad    reads dx3                  writes dX2 (+ bn2's backward statistics)
+//   conv3 wgrad    reads dx3, y2              writes fp32 split-K partials
+// dx3 = a[c]*(g*mask) + b[c]*x3 + k[c] (bn_bwd_finalize's coef), rounded to bf16, is pure
+// intermediate.  Here each block streams g and x3 ONCE: per 64-pixel tile it forms the
+// bf16 dx3 tile in LDS (the same expression and rounding as bn_bwd_apply) and feeds both
+// products from that image:
+//   dX2 tile  = dx3 . W      pixel rows = A operand (ds_read_b128), k = co ascending in
+//                            steps of 32 as conv_igemm_kernel walks it; W = the dgrad's
+//                            transposed weight [Ci][Co], in LDS (below)
+//   dW       += dx3^T . y2   both operands k(pixel)-major, read with ds_read_b64_tr_b16 as
+//                            in wgrad.hip; y2 tile by LDS-DMA; dW lives in registers for the
+//                            block's whole pixel range (64 / 128 fp32 per lane)
+// so 2T + 3t bytes move instead of 5T + 3t (T = K*Co*2, t = T/4).
+//
+// Blocks (4 Ci threads) are persistent: block b owns one contiguous range of whole 64-pixel
+// tiles and writes ONE complete fp32 dW partial [Co][Ci] at the end (slab b);
+// wgrad_reduce_kernel then sums the slabs into the flat gradient.  No block waits for another.
+//
+// LDS image of the dx3 tile: Co / 128 [64 pixel][128 co] sub-images with tile.h's img_swz<128>
+// chunk swizzle.  Both read patterns are conflict-free under it: the transposed reads by
+// construction (wgrad.hip), and the 16 pixel rows of a ds_read_b128 fragment read (one
+// logical chunk, 16 consecutive rows) land in 16 distinct chunks of the 256-B bank cycle,
+// because img_swz<128> is a bijection of row & 15.
+//
+// Weight: a [Ci][256 co] slot (512-B rows, chunk ^ (ci & 15)).  Ci = 64: the whole weight
+// (32 KB), loaded once, resident.  Ci = 128: the 128 KB weight does not fit beside the tiles;
+// its two 256-co halves (64 KB each) pass through the slot once per tile from L2 by
+// LDS-DMA, the first under the wgrad's MFMAs, the second exposed (one slot).
+//
+// LDS: Ci = 64: image 32 + W 32 + y2 8 + coef 3 = 75 KB, two blocks per CU;
+//      Ci = 128: image 64 + W slot 64 + y2 16 + coef 6 = 150 KB, one block (8 waves) per CU.
+// Registers: Ci = 64 keeps the whole next tile's g / x3 / bits loads (72 VGPRs) in flight
+// under the current tile's MFMAs and epilogue.  Ci = 128 holds 128 dW registers per lane: with
+// 256 per lane at two waves per SIMD the next tile's loads are issued after the epilogue
+// (only the y2 DMA, which needs no registers, runs ahead).
+// The epilogue stages each wave's dX2 rows in the image rows that wave itself wrote:
+// no other wave writes there, and every wave's reads of the image are behind a barrier by then.
+// Rows past K: g / x3 / y2 read 0 through the buffer range check (the dx3 rows are then
+// k[c], multiplied by y2 = 0 in dW; their dX2 rows are dropped by the epilogue's range check).
+#include "common.h"
+#include "tile.h"
+#include "conv_epilogue.h"
+
+int kfa_wgrad_reduce_launch(const float* part, int splits, long total, void* grad, int grad_f32, int accumulate,
+                            hipStream_t s);  // wgrad.hip
+
+namespace {
+using namespace tile;
+
+constexpr int TP = 64;  // pixels per tile
+
+__device__ __forceinline__ unsigned lds_addr(const void* p) {
+  return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
+}
+// ds_read_b128 at la + OFF (inline asm, as conv_igemm_kernel's fragment reads: ordered by the
+// kernel's own lgkmcnt waits; OFF folded into the instruction so a fragment costs no address VGPR)
+template <int OFF>
+__device__ __forceinline__ short8 lds_rd16(unsigned la) {
+  short8 v;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(la), "i"(OFF) : "memory");
+  return v;
+}
+
+template <int CI>
+__global__ __launch_bounds__(4 * CI, CI == 64 ? 2 : 1) void conv3_bwd_fused_kernel(
+    const bf16_t* __restrict__ G, const bf16_t* __restrict__ X3, const uint8_t* __restrict__ MB,
+    const float* __restrict__ coef, const bf16_t* __restrict__ Y2, const bf16_t* __restrict__ Wt,
+    bf16_t* __restrict__ DX2, float* __restrict__ part, float* __restrict__ stats, BnBwd bnb, Geo g) {
+  static_assert(CI == 64 || CI == 128, "LDS and register budgets are laid out for Ci = 64 / 128");
+  constexpr int CO = 4 * CI, NT = 4 * CI, NW = NT / 64;
+  constexpr int CPR = CO / 8;             // 16-B chunks per dx3 row (32 / 64)
+  constexpr int LR = TP * CPR / NT;       // 16-B g / x3 loads per lane per tile (8)
+  constexpr int RPW = TP / NW;            // image rows a wave fills (16 / 8)
+  constexpr int RSTEP = 64 / CPR;         // rows one wave instruction covers (2 / 1)
+  constexpr int SUB = TP * 128;           // elements of one [64][128] sub-image
+  constexpr int WH = CO / 256;            // 256-co weight halves passing through the slot (1: resident)
+  constexpr int WL = CI * 32 / NT;        // 16-B loads per lane per weight half (8)
+  constexpr int TNW = CI / 16;            // wgrad ci tiles per wave (4 / 8)
+  constexpr bool PREFETCH = CI == 64;     // next tile's register loads under this tile's MFMAs + epilogue
+  static_assert(LR * RSTEP == RPW, "a wave's loads cover its own image rows");
+  __shared__ __attribute__((aligned(16))) bf16_t s_img[TP * CO];
+  __shared__ __attribute__((aligned(16))) bf16_t s_w[CI * 256];
+  __shared__ __attribute__((aligned(16))) bf16_t s_y[TP * CI];
+  __shared__ __attribute__((aligned(16))) float s_coef[3 * CO];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wp = wave & 3, wc = wave >> 2;  // dgrad wave tile: pixels 16 wp .., ci 64 wc ..
+  // pixel ownership: whole tiles, dealt contiguously (the first `rem` blocks get one more)
+  const int ntiles = (g.M + TP - 1) / TP, nb = gridDim.x, b = blockIdx.x;
+  const int base = ntiles / nb, rem = ntiles % nb;
+  const int t0 = b * base + (b < rem ? b : rem), nt = base + (b < rem ? 1 : 0);
+  if (nt == 0) return;
+
+  const unsigned big_bytes = (unsigned)g.M * (unsigned)CO * 2u;
+  const __amdgpu_buffer_rsrc_t rG = rsrc(G, big_bytes), rX = rsrc(X3, big_bytes);
+  const __amdgpu_buffer_rsrc_t rM = rsrc(MB, big_bytes >> 4);
+  const __amdgpu_buffer_rsrc_t rY = rsrc(Y2, g.d_bytes), rD = rsrc(DX2, g.d_bytes);
+  const __amdgpu_buffer_rsrc_t rBX = rsrc(bnb.x ? bnb.x : DX2, bnb.x ? g.d_bytes : 0u);
+  const EpiRes er{rD, rsrc(DX2, 0u), rBX, rsrc(DX2, 0u)};
+
+  // weight half h into the slot: row ci, 16-B chunk c (of the half's 32) stored at c ^ (ci & 15)
+  // (the 16 rows of a fragment read then hit 16 distinct chunks of one 256-B bank cycle)
+  // (Ci = 128: by LDS-DMA, no registers: wave instruction j = WL wave + i fills rows 2j, 2j + 1
+  // lane-linearly, the swizzle applied on the per-lane source address)
+  const __amdgpu_buffer_rsrc_t rW = rsrc(Wt, g.b_bytes);
+  auto w_dma = [&](int h) __attribute__((always_inline)) {
+    int lx = lane;  // source offsets formed per use, not carried across the tile loop
+    asm volatile("" : "+v"(lx));
+    static_for<WL>([&](auto ic) __attribute__((always_inline)) {
+      constexpr int i = decltype(ic)::value;
+      const int row = (wave * WL + i) * 2 + (lx >> 5);
+      const int vo = (row * CO + (((lx & 31) ^ (row & 15)) << 3)) * 2;
+      buf_dma16(rW, s_w + (wave * WL + i) * 512, vo, h * 512);
+    });
+  };
+  if constexpr (WH == 1) {  // resident: straight through (the staged form's register array would sit in scratch here)
+#pragma unroll
+    for (int i = 0; i < WL; i++) {
+      const int id = i * NT + tid, row = id >> 5, c = id & 31;
+      const uint4 v = *reinterpret_cast<const uint4*>(Wt + row * CO + c * 8);
+      *reinterpret_cast<uint4*>(s_w + row * 256 + ((c ^ (row & 15)) << 3)) = v;
+    }
+  }
+  for (int i = tid; i < 3 * CO; i += NT) s_coef[i] = coef[i];
+  __syncthreads();
+  // prologue plan: load i of a lane is row RPW*wave + RSTEP*i + lane / CPR, chunk lane % CPR (fixed
+  // per lane: its 8 channels' coefficients are re-read from LDS per tile, not held in registers)
+  const unsigned pvo = (unsigned)((RPW * wave + lane / CPR) * CO + (lane % CPR) * 8) * 2u;  // byte offset within a tile
+  // y2 plan (wgrad.hip's staging): a wave instruction fills 1 KB = 512 / CI rows, physical chunk
+  // lane % (CI/8) <- logical chunk ^ img_swz<CI>(row), applied on the source address
+  constexpr int YRPI = 512 / CI, YCPR = CI / 8;
+  constexpr int YI = TP / YRPI / NW;  // y2 DMA instructions per wave per tile (2)
+  int y_vo[YI];
+#pragma unroll
+  for (int i = 0; i < YI; i++) {
+    const int row = (wave * YI + i) * YRPI + lane / YCPR;
+    y_vo[i] = (row * CI + (((lane % YCPR) ^ img_swz<CI>(row)) << 3)) * 2;
+  }
+
+  uint4 gv[LR], xv[LR];
+  unsigned bits[LR];
+  auto issue_regs = [&](int t) __attribute__((always_inline)) {
+    const unsigned so = (unsigned)t * (unsigned)(TP * CO * 2);
+#pragma unroll
+    for (int i = 0; i < LR; i++) {
+      const unsigned vo = pvo + (unsigned)(i * RSTEP * CO * 2);
+      gv[i] = bload16<2>(rG, vo + so);
+      bits[i] = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rM, (vo + so) >> 4, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < LR; i++) xv[i] = bload16<2>(rX, pvo + (unsigned)(i * RSTEP * CO * 2) + so);
+  };
+  auto issue_y = [&](int t) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < YI; i++)
+      buf_dma16(rY, s_y + (wave * YI + i) * YRPI * CI, y_vo[i], t * (TP * CI * 2));
+  };
+
+  floatx4 accw[TNW][4], accd[4][1];
+#pragma unroll
+  for (int i = 0; i < 4; i++) accd[i][0] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < TNW; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) accw[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+
+  // dgrad over weight half h: accd[ni][0] = D(pixel 16 wp + fr, ci 64 wc + 16 ni + 4 fq + r),
+  // k = co ascending.  k-step j of the half reads logical chunk 4 j + fq of the pixel / weight
+  // rows: the swizzles touch the chunk's low 4 bits only, so j & 3 picks one of four per-lane
+  // bases and the sub-image, the weight row's second 256 B and ni are immediates
+  auto dgrad_half = [&](auto hc) __attribute__((always_inline)) {
+    constexpr int h = decltype(hc)::value;
+    int ld = lane;  // fragment bases formed per use, not carried across the tile loop
+    asm volatile("" : "+v"(ld));
+    const int fr = ld & 15, fq = ld >> 4;
+    static_for<8>([&](auto jc) __attribute__((always_inline)) {
+      constexpr int j = decltype(jc)::value, q = j & 3, hi = j >> 2;
+      const unsigned ch = (unsigned)(q * 4 + fq);
+      const unsigned a_la = lds_addr(s_img) + (unsigned)img_off<128>(wp * 16 + fr, (int)ch * 8);
+      const unsigned w_la = lds_addr(s_w) + (unsigned)((wc * 64 + fr) * 512) + ((ch ^ (unsigned)fr) << 4);
+      short8 bf[4];
+      const short8 af = lds_rd16<(h * 2 + hi) * SUB * 2>(a_la);
+      bf[0] = lds_rd16<hi * 256 + 0 * 16 * 512>(w_la);
+      bf[1] = lds_rd16<hi * 256 + 1 * 16 * 512>(w_la);
+      bf[2] = lds_rd16<hi * 256 + 2 * 16 * 512>(w_la);
+      bf[3] = lds_rd16<hi * 256 + 3 * 16 * 512>(w_la);
+      lgkm_wait<0>();
+      __builtin_amdgcn_sched_barrier(0);
+      // (spelled out: inside nested lambdas `#pragma unroll` is not honoured, and a runtime
+      // index sends the arrays to scratch)
+      accd[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[0], af, accd[0][0], 0, 0, 0);
+      accd[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[1], af, accd[1][0], 0, 0, 0);
+      accd[2][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[2], af, accd[2][0], 0, 0, 0);
+      accd[3][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[3], af, accd[3][0], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+  };
+  // wgrad: accw[ni][mi] = dW(co 64 wave + 16 mi + fr, ci 16 ni + 4 fq + r), k = the tile's pixels
+  auto wgrad = [&]() __attribute__((always_inline)) {
+    const bf16_t* asub = s_img + (wave >> 1) * SUB;
+    const int cb0 = (wave & 1) * 64;
+    int lw = lane;  // operand addresses formed per tile, not carried across the tile loop
+    asm volatile("" : "+v"(lw));
+    static_for<2>([&](auto kc) __attribute__((always_inline)) {
+      constexpr int ks = decltype(kc)::value;
+      short8 af[4];
+      static_for<4>([&](auto mc) __attribute__((always_inline)) {
+        constexpr int mi = decltype(mc)::value;
+        af[mi] = tr_operand_asm<128, ks>(asub, cb0 + mi * 16, lw);
+      });
+      constexpr int NG = CI == 64 ? 4 : 2;  // ci tiles per group of reads (Ci = 128 is at the VGPR limit)
+      static_for<TNW / NG>([&](auto nc) __attribute__((always_inline)) {
+        constexpr int n0 = decltype(nc)::value * NG;
+        short8 bf[NG];
+        static_for<NG>([&](auto ic) __attribute__((always_inline)) {
+          constexpr int ni = decltype(ic)::value;
+          bf[ni] = tr_operand_asm<CI, ks>(s_y, (n0 + ni) * 16, lw);
+        });
+        lgkm_wait<0>();
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<4 * NG>([&](auto ic) __attribute__((always_inline)) {
+          constexpr int ni = decltype(ic)::value >> 2, mi = decltype(ic)::value & 3;
+          accw[n0 + ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[ni], af[mi], accw[n0 + ni][mi], 0, 0, 0);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+      });
+    });
+  };
+
+  issue_y(t0);
+  issue_regs(t0);
+  for (int it = 0; it < nt; it++) {
+    const int t = t0 + it;
+    // dx3 tile -> LDS image (bn_bwd_apply's expression and rounding)
+    int lc = lane;  // (image addresses formed per tile)
+    asm volatile("" : "+v"(lc));
+    const int pc = lc % CPR, pr = RPW * wave + lc / CPR;
+    float ca[8], cb[8], ck[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      ca[j] = s_coef[pc * 8 + j];
+      cb[j] = s_coef[CO + pc * 8 + j];
+      ck[j] = s_coef[2 * CO + pc * 8 + j];
+    }
+#pragma unroll
+    for (int i = 0; i < LR; i++) {
+      float gf[8], xf[8], o[8];
+      unpack8(gv[i], gf);
+      unpack8(xv[i], xf);
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const float dz = ((bits[i] >> j) & 1u) ? gf[j] : 0.f;
+        o[j] = fmaf(ca[j], dz, fmaf(cb[j], xf[j], ck[j]));
+      }
+      const int row = i * RSTEP + pr;
+      *reinterpret_cast<uint4*>(reinterpret_cast<char*>(s_img + (pc >> 4) * SUB) + img_off<128>(row, (pc & 15) * 8)) =
+          pack8(o);
+    }
+    vm_wait<0>();  // this tile's y2 DMA landed (the youngest load in flight; the last tile's stores drain too)
+    if constexpr (PREFETCH)
+      if (it + 1 < nt) issue_regs(t + 1);  // the whole next tile in flight under this tile's MFMAs and epilogue
+    lds_barrier();                         // image and y2 tile published (also the resident weight)
+
+    if constexpr (WH == 1) {
+      dgrad_half(std::integral_constant<int, 0>{});
+      wgrad();
+    } else {
+      // (every wave left the last tile's second-half reads of the slot behind that tile's last barrier)
+      w_dma(0);
+      wgrad();  // half 0 lands under the wgrad's MFMAs
+      vm_wait<0>();
+      lds_barrier();
+#pragma unroll
+      for (int i = 0; i < 4; i++) accd[i][0] = floatx4{0.f, 0.f, 0.f, 0.f};  // (not live across the wgrad)
+      dgrad_half(std::integral_constant<int, 0>{});
+      lds_barrier();  // every wave is done reading half 0
+      w_dma(1);       // (one slot: this half's L2 latency is exposed)
+      vm_wait<0>();
+      lds_barrier();
+      dgrad_half(std::integral_constant<int, 1>{});
+    }
+    lds_barrier();  // every wave is done reading the image, the y2 tile and the weight slot
+    if (it + 1 < nt) issue_y(t + 1);
+    // dX2 tile out (LDS-staged 16-B stores, bn2's backward statistics), staged in this wave's own image rows
+    // (the statistics' per-channel operands and the epilogue's lane-derived offsets are
+    // re-formed per tile: hoisted out of the tile loop they were held in scratch)
+    BnBwd bt = bnb;
+    int le = lane;
+    asm volatile("" : "+s"(bt.mean), "+s"(bt.ss), "+v"(le));
+    conv_epilogue<1, 4, 1, kEpiStats | kEpiBnBwd>(g, accd, reinterpret_cast<char*>(s_img + RPW * wave * 128), false,
+                                                  le, t * TP + wp * 16, wc * 64, 1, 1.f, 1.f, true, nullptr, stats, bt,
+                                                  er);
+    if constexpr (!PREFETCH)
+      if (it + 1 < nt) issue_regs(t + 1);
+  }
+
+  // this block's complete dW partial (slab b)
+  float* slab = part + (long)b * (CO * CI);
+#pragma unroll
+  for (int ni = 0; ni < TNW; ni++)
+#pragma unroll
+    for (int mi = 0; mi < 4; mi++) {
+      const int m = wave * 64 + mi * 16 + (lane & 15), n = ni * 16 + (lane >> 4) * 4;
+      *reinterpret_cast<floatx4*>(slab + m * CI + n) = accw[ni][mi];
+    }
+}
+
+bool fused_shape_ok(int Ci, int Co, int R, int S, int stride, int pad) {
+  return R == 1 && S == 1 && stride == 1 && pad == 0 && (Ci == 64 || Ci == 128) && Co == 4 * Ci;
+}
+
+// blocks with a non-empty pixel range = fp32 partial slabs
+int fused_blocks(long K, int Ci, int max_blocks) {
+  const long ntiles = (K + TP - 1) / TP;
+  const long cap = max_blocks > 0 ? max_blocks : (Ci == 64 ? 2L : 1L) * kfa_cu_count();
+  return (int)(ntiles < cap ? ntiles : cap);
+}
+
+}  // namespace
+
+// floats of the split-K partial workspace kfa_conv3_bwd_fused needs (0: shape not covered)
+KFA_API long kfa_conv3_bwd_part_floats(int Nb, int P, int Q, int Co, int Ci, int max_blocks) {
+  if (!fused_shape_ok(Ci, Co, 1, 1, 1, 0)) return 0;
+  return (long)fused_blocks((long)Nb * P * Q, Ci, max_blocks) * Co * Ci;
+}
+
+// bn3 backward apply + conv3 dgrad + conv3 wgrad in one pass (see the top of this file).
+//   g, x3 [K][Co] bf16, mb: bn3's ReLU bits (K*Co/8 bytes), coef [3][Co] (kfa_bn_bwd_finalize_only),
+//   y2 [K][Ci], wt [Ci][Co] (the dgrad's transposed weight), dx2 [K][Ci] out,
+//   grad [Co][Ci] (bf16 / fp32; accumulate as kfa_conv_wgrad), part: kfa_conv3_bwd_part_floats floats,
+//   stats + bn_*: bn2's slot workspace and backward-statistics operands (all null: no statistics),
+//   max_blocks: 0 = two blocks per CU (Ci = 64) / one (Ci = 128).
+// -1: shape not covered (1x1 / stride 1 / pad 0, Ci = 64 / 128, Co = 4 Ci only), -2: 32-bit offset limits.
+KFA_API int kfa_conv3_bwd_fused(const bf16_t* g, const bf16_t* x3, const uint8_t* mb, const float* coef,
+                                const bf16_t* y2, const bf16_t* wt, bf16_t* dx2, void* grad, int grad_f32,
+                                int accumulate, float* part, int Nb, int P, int Q, int Ci, int Co, int R, int S,
+                                int stride, int pad, float* stats, const bf16_t* bn_x, const float* bn_mean,
+                                int bn_relu, const float* bn_ss, const uint8_t* bn_mb, int max_blocks,
+                                hipStream_t s) {
+  if (!fused_shape_ok(Ci, Co, R, S, stride, pad)) return -1;
+  if (!g || !x3 || !mb || !coef || !y2 || !wt || !dx2 || !grad || !part) return -1;
+  if (bn_x && bn_relu && !bn_ss && !bn_mb) return -3;
+  const long K = (long)Nb * P * Q;
+  if (K <= 0) return 0;
+  if (K >= (1L << 24) || K * Co * 2 >= (long)kOOB) return -2;
+  Geo geo{Nb, P, Q, Co, P, Q, 1, 1, 1, 1, 0, 0, (int)K, Ci, Co, P, Q, 1, 0, 0, Ci,
+          (unsigned)(K * Co * 2), (unsigned)((long)Ci * Co * 2), (unsigned)(K * Ci * 2)};
+  const BnBwd bnb{bn_x, nullptr, bn_ss, bn_mb, bn_mean, bn_relu, nullptr};
+  const int blocks = fused_blocks(K, Ci, max_blocks);
+  float* st = bn_x ? stats : nullptr;
+  if (Ci == 64)
+    hipLaunchKernelGGL(conv3_bwd_fused_kernel<64>, dim3(blocks), dim3(256), 0, s, g, x3, mb, coef, y2, wt, dx2, part,
+                       st, bnb, geo);
+  else
+    hipLaunchKernelGGL(conv3_bwd_fused_kernel<128>, dim3(blocks), dim3(512), 0, s, g, x3, mb, coef, y2, wt, dx2,
+                       part, st, bnb, geo);
+  const int rc = kfa_status();
+  if (rc) return rc;
+  return kfa_wgrad_reduce_launch(part, blocks, (long)Co * Ci, grad, grad_f32, accumulate, s);
+}

@@ -112,6 +112,51 @@ __device__ __forceinline__ int swz_chunk(int row) { return (row >> 1) & 7; }
 // element offset of (row, logical 16-B chunk) in such an image
 __device__ __forceinline__ int swz128(int row, int chunk) { return row * 64 + ((chunk ^ swz_chunk(row)) << 3); }
 
+// ---- k-major operand images (wgrad.hip, conv3_bwd.hip) -------------------------
+typedef short v4i16 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
+
+// [k][WIDTH] bf16 LDS images (WIDTH = 128 or 64 elements = 256 / 128-B rows),
+// 16-B chunks XOR-swizzled so both the lane-linear DMA fill and the
+// ds_read_b64_tr_b16 operand reads are conflict-free:
+//   256-B rows: chunk ^ (((row&3)<<2) | ((row>>2)&3))           (16 chunks)
+//   128-B rows: chunk ^ 2*(((row>>1)&1) | (((row>>3)&1)<<1))     (8 chunks; keeps 32-B pairs)
+template <int WIDTH>
+__device__ __forceinline__ int img_swz(int row) {
+  if constexpr (WIDTH == 128) return ((row & 3) << 2) | ((row >> 2) & 3);
+  else return 2 * (((row >> 1) & 1) | (((row >> 3) & 1) << 1));
+}
+template <int WIDTH>
+__device__ __forceinline__ int img_off(int row, int col) {  // byte offset of element (row, col)
+  return WIDTH * 2 * row + 16 * ((col >> 3) ^ img_swz<WIDTH>(row)) + 2 * (col & 7);
+}
+
+// The transposed read as inline asm, for hand-counted kernels:
+// hipcc puts an s_waitcnt vmcnt(0) in front of every compiler-visible
+// ds_read_b64_tr_b16 that follows an LDS-DMA into the same array (it cannot tell
+// the pieces apart), draining the whole DMA pipeline once per phase; the asm form
+// is ordered by the kernel's own counted vmcnt + s_barrier + lgkmcnt(0) instead.
+// OFF: the read's constant byte offset (piece and k-half), folded into the instruction.
+template <int OFF>
+__device__ __forceinline__ v4i16 ds_tr16(unsigned addr) {
+  v4i16 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF) : "memory");
+  return v;
+}
+
+// MFMA operand (8 consecutive k of one column: rows 8g + q and 8g + 4 + q, columns
+// cb + 4p, T10 lane map) through ds_tr16: k-half KS's row offset (32 rows; the
+// swizzle repeats every 16) as the immediate
+template <int WIDTH, int KS>
+__device__ __forceinline__ short8 tr_operand_asm(const bf16_t* tile, int cb, int lane) {
+  const int g = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3;
+  const int col = cb + 4 * p, r0 = 8 * g + q;
+  const unsigned b = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const bf16_t*)tile;
+  const v4i16 a = ds_tr16<KS * 32 * WIDTH * 2>(b + (unsigned)img_off<WIDTH>(r0, col));
+  const v4i16 c = ds_tr16<KS * 32 * WIDTH * 2>(b + (unsigned)img_off<WIDTH>(r0 + 4, col));
+  return short8{a[0], a[1], a[2], a[3], c[0], c[1], c[2], c[3]};
+}
+
 // Compile-time loop: f(std::integral_constant<int, 0>) ... f(<N-1>) — keeps
 // register-array indices constant where `#pragma unroll` is not honoured
 // (a runtime index sends the whole accumulator array to scratch).

@@ -49,24 +49,8 @@ struct WGeo {
 #define KFA_WG_X_AUX 0  // ... and of the X operand's
 #endif
 
-typedef short v4i16 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
-
-// [k][WIDTH] bf16 LDS images (WIDTH = 128 or 64 elements = 256 / 128-B rows),
-// 16-B chunks XOR-swizzled so both the lane-linear DMA fill and the
-// ds_read_b64_tr_b16 operand reads are conflict-free:
-//   256-B rows: chunk ^ (((row&3)<<2) | ((row>>2)&3))           (16 chunks)
-//   128-B rows: chunk ^ 2*(((row>>1)&1) | (((row>>3)&1)<<1))     (8 chunks; keeps 32-B pairs)
-template <int WIDTH>
-__device__ __forceinline__ int img_swz(int row) {
-  if constexpr (WIDTH == 128) return ((row & 3) << 2) | ((row >> 2) & 3);
-  else return 2 * (((row >> 1) & 1) | (((row >> 3) & 1) << 1));
-}
-template <int WIDTH>
-__device__ __forceinline__ int img_off(int row, int col) {  // byte offset of element (row, col)
-  return WIDTH * 2 * row + 16 * ((col >> 3) ^ img_swz<WIDTH>(row)) + 2 * (col & 7);
-}
-
+// The [k][WIDTH] image layout (img_swz / img_off) and the inline-asm transposed reads
+// (ds_tr16, tr_operand_asm) are tile.h's.
 // MFMA operand (8 consecutive k of one column) via two transposed reads:
 // rows kb + 8g + q and kb + 8g + 4 + q, columns cb + 4p (T10 lane map).
 template <int WIDTH>
@@ -78,31 +62,6 @@ __device__ __forceinline__ short8 tr_operand(const bf16_t* tile, int kb, int cb,
   const v4i16 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(base + img_off<WIDTH>(r0, col)));
   const v4i16 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(base + img_off<WIDTH>(r0 + 4, col)));
   return short8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-
-// The same transposed read as inline asm, for the hand-counted ping-pong kernel:
-// hipcc puts an s_waitcnt vmcnt(0) in front of every compiler-visible
-// ds_read_b64_tr_b16 that follows an LDS-DMA into the same array (it cannot tell
-// the pieces apart), draining the whole DMA pipeline once per phase; the asm form
-// is ordered by the kernel's own counted vmcnt + s_barrier + lgkmcnt(0) instead.
-// OFF: the read's constant byte offset (piece and k-half), folded into the instruction.
-template <int OFF>
-__device__ __forceinline__ v4i16 ds_tr16(unsigned addr) {
-  v4i16 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF) : "memory");
-  return v;
-}
-
-// tr_operand through ds_tr16: k-half KS's row offset (32 rows; the swizzle repeats
-// every 16) as the immediate
-template <int WIDTH, int KS>
-__device__ __forceinline__ short8 tr_operand_asm(const bf16_t* tile, int cb, int lane) {
-  const int g = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3;
-  const int col = cb + 4 * p, r0 = 8 * g + q;
-  const unsigned b = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const bf16_t*)tile;
-  const v4i16 a = ds_tr16<KS * 32 * WIDTH * 2>(b + (unsigned)img_off<WIDTH>(r0, col));
-  const v4i16 c = ds_tr16<KS * 32 * WIDTH * 2>(b + (unsigned)img_off<WIDTH>(r0 + 4, col));
-  return short8{a[0], a[1], a[2], a[3], c[0], c[1], c[2], c[3]};
 }
 
 // WM x WN waves, each TM x TN MFMA 16x16 tiles: block tile BM = 16*WM*TM output
@@ -877,6 +836,16 @@ KFA_API long kfa_wgrad_part_floats(int Nb, int P, int Q, int Co, int R, int S, i
   const WPlan p0 = plan((long)Nb * P * Q, Co, R * S * Ci), p1 = plan((long)Nb * P * Q, Co, R * S * Ci, R == 1 && S == 1);
   const WPlan& p = p0.splits >= p1.splits ? p0 : p1;
   return p.splits > 1 ? (long)p.splits * Co * R * S * Ci : 0;
+}
+
+// grad (+)= sum over `splits` fp32 partial slabs of `total` floats each (wgrad_reduce_kernel):
+// the second half of every split-K weight gradient, also of conv3_bwd.hip's fused kernel.
+int kfa_wgrad_reduce_launch(const float* part, int splits, long total, void* grad, int grad_f32, int accumulate,
+                            hipStream_t s) {
+  const long blocks = (total / 4 + 63) / 64;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, part, splits, total, grad, grad_f32,
+                     accumulate);
+  return kfa_status();
 }
 
 // dW (+)= conv weight gradient, written into `grad` ([Co][R][S][Ci], bf16 or fp32).

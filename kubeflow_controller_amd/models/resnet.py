@@ -63,7 +63,10 @@ class Bottleneck(nn.Module):
         if self.downsample is None:
             y = self.bn1(self.conv1(x, join=join, bn_stats=st), bwd_link=st)
             y = self.bn2(self.conv2(y, bn_stats=st), bwd_link=st, lazy=st and LAZY_BN2)
-            return self.bn3(self.conv3(y, bn_stats=st), residual=join.branch(x), bwd_link=st, res_join=join)
+            # conv3's output feeds bn3 alone: bn3's backward may leave its input gradient to conv3's
+            # one-pass backward (ops.conv.Conv3BwdLink; identity blocks only)
+            return self.bn3(self.conv3(y, bn_stats=st, tail_link=st), residual=join.branch(x), bwd_link=st,
+                            res_join=join)
         # downsample block: relu(bn3(.) + bn_ds(.)) in ONE apply pass each way
         # (ops.batchnorm.bn_act_dual): the downsample conv's statistics wait in
         # their own slot workspace while conv1..conv3 fill the shared one.

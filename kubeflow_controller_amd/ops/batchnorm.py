@@ -48,6 +48,9 @@ _lib.register("kfa_bn_fwd_train_dual", [_lib.P] * 11 + [_lib.L, _lib.I, _lib.F, 
                                                         _lib.I, _lib.P])
 _lib.register("kfa_bn_bwd_rstats", [_lib.P] * 11 + [_lib.L, _lib.I, _lib.I, _lib.I] + [_lib.P] * 5 + [_lib.I, _lib.P])
 _lib.register("kfa_bn_apply_ss", [_lib.P, _lib.P, _lib.P, _lib.L, _lib.I, _lib.I, _lib.P])
+# dy x y gamma mean invstd dgamma dbeta slots coef | M C relu accumulate | ss mb | prestats | stream
+_lib.register("kfa_bn_bwd_finalize_only", [_lib.P] * 10 + [_lib.L, _lib.I, _lib.I, _lib.I, _lib.P, _lib.P, _lib.I,
+                                                          _lib.P])
 
 
 class LazyBN:
@@ -115,7 +118,7 @@ def _workspaces(C: int, device):
 class _BNActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, residual, training, momentum, eps, relu,
-                prestats=False, link=None, res_join=None, lazy=None):
+                prestats=False, link=None, res_join=None, lazy=None, tail=None):
         x = _as_rows(x)
         M, C = _mc(x)
         if x.dtype != torch.bfloat16:
@@ -166,6 +169,9 @@ class _BNActFn(torch.autograd.Function):
         # itself: the backward then skips writing dres (2 of its ~8 bytes per element)
         ctx.res_join = res_join if (training and mb is not None and residual is not None) else None
         ctx.params = (weight, bias)
+        # x = the output of a conv that armed a Conv3BwdLink: this backward may leave dx to it
+        # (training, ReLU with residual bits; the dual / downsample form never gets here)
+        ctx.tail = tail if (tail is not None and training and relu and mb is not None and tail.take()) else None
         return y
 
     @staticmethod
@@ -193,17 +199,30 @@ class _BNActFn(torch.autograd.Function):
         if lk is not None:
             lk.prestats = False
             lk.x = lk.y = lk.ss = lk.mb = lk.mean = None
-        _lib.call("kfa_bn_bwd_prestats" if pre else "kfa_bn_bwd", _lib.ptr(dy), _lib.ptr(x), _lib.ptr(y), _lib.ptr(weight), _lib.ptr(mean),
-                  _lib.ptr(invstd), _lib.ptr(dx), _lib.ptr(dres), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(slots),
-                  _lib.ptr(coef),
-                  M, C, int(ctx.relu), int(direct), _lib.ptr(ss), _lib.ptr(mb), _lib.stream())
+        tail = ctx.tail
+        # (a second backward over a retained graph finds the link used up: the ordinary pass then)
+        if tail is not None and tail.state == "taken" and dres is None and ctx.needs_input_grad[0]:
+            # finalize only, into a coef buffer the link owns (the shared one is rewritten by the
+            # next BatchNorm backward); dx stays UNWRITTEN: the producing conv's backward forms it
+            # per tile (ops.conv.Conv3BwdLink), or writes it with the apply pass if it cannot
+            tcoef = torch.empty(3 * C, dtype=torch.float32, device=x.device)
+            _lib.call("kfa_bn_bwd_finalize_only", _lib.ptr(dy), _lib.ptr(x), _lib.ptr(y), _lib.ptr(weight),
+                      _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(slots),
+                      _lib.ptr(tcoef), M, C, int(ctx.relu), int(direct), _lib.ptr(ss), _lib.ptr(mb), int(pre),
+                      _lib.stream())
+            tail.defer(dy, x, mb, tcoef, dx, bool(ctx.relu))
+        else:
+            _lib.call("kfa_bn_bwd_prestats" if pre else "kfa_bn_bwd", _lib.ptr(dy), _lib.ptr(x), _lib.ptr(y),
+                      _lib.ptr(weight), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(dx), _lib.ptr(dres),
+                      _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(slots), _lib.ptr(coef),
+                      M, C, int(ctx.relu), int(direct), _lib.ptr(ss), _lib.ptr(mb), _lib.stream())
         if direct:
             notify_grad_ready(ctx.params[0])
             notify_grad_ready(ctx.params[1])
-            return dx, None, None, None, None, dres, None, None, None, None, None, None, None, None
+            return dx, None, None, None, None, dres, None, None, None, None, None, None, None, None, None
         if dgamma is not None and weight is not None and weight.dtype != torch.float32:
             dgamma, dbeta = dgamma.to(weight.dtype), dbeta.to(weight.dtype)
-        return dx, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None, None
+        return dx, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None, None, None
 
 
 def bn_act(x, weight, bias, running_mean, running_var, residual=None, training=True, momentum=0.1, eps=1e-5,
@@ -219,8 +238,9 @@ def bn_act(x, weight, bias, running_mean, running_var, residual=None, training=T
         prestats = False
     link = BnBwdLink() if (bwd_link and training) else None
     lz = LazyBN() if (lazy and training and relu and residual is None and MASK_FROM_X and x.is_cuda) else None
+    tail = getattr(x, "_kfa_conv3_link", None) if (training and residual is not None) else None
     y = _BNActFn.apply(x, weight, bias, running_mean, running_var, residual, training, momentum, eps, relu,
-                       prestats, link, res_join, lz)
+                       prestats, link, res_join, lz, tail)
     if link is not None:
         y._kfa_bn_link = link
     if lz is not None and lz.pending:

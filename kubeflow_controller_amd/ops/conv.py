@@ -126,6 +126,11 @@ _lib.register("kfa_bn_stats_partial", [P, P, _lib.L, I, P])
 _lib.register("kfa_stem_s2d", [P, P, I, I, I, I, I, P])
 _lib.register("kfa_stem_weight_s2d", [P, P, I, I, I, I, P])
 _lib.register("kfa_stem_wgrad_fold", [P, P, I, I, I, I, I, I, P])
+# g x3 mb coef y2 wt dx2 grad | grad_f32 accumulate | part | Nb P Q Ci Co R S stride pad | stats bn_x bn_mean |
+# bn_relu | bn_ss bn_mb | max_blocks | stream
+_lib.register("kfa_conv3_bwd_fused", [P] * 8 + [I, I, P] + [I] * 9 + [P, P, P, I, P, P, I, P])
+_lib.register("kfa_conv3_bwd_part_floats", [I] * 6, _lib.L)
+_lib.register("kfa_bn_bwd_apply_only", [P] * 5 + [_lib.L, I, I, P, P, P])
 
 # Runtime switches (tests compare against the vendor path); env KFA_CONV_IGEMM=0 / KFA_WGRAD=0 disable.
 ENABLED = os.environ.get("KFA_CONV_IGEMM", "1") != "0"
@@ -133,6 +138,11 @@ WGRAD_ENABLED = os.environ.get("KFA_WGRAD", "1") != "0"
 # KFA_CONV_WGRAD_SIDE=1: conv weight gradients on the side stream (ops/streams.py),
 # concurrent with the data-gradient chain (dgrad convs, BatchNorm backward passes)
 WGRAD_SIDE = os.environ.get("KFA_CONV_WGRAD_SIDE", "0") == "1"
+
+
+# One-pass bn3 backward + conv3 dgrad / wgrad for identity bottleneck tails (csrc/kernels/conv3_bwd.hip,
+# ``Conv3BwdLink``); KFA_CONV3_BWD_FUSED=0 keeps apply + dgrad + wgrad + reduce.  Tests flip the attribute.
+CONV3_BWD_FUSED = os.environ.get("KFA_CONV3_BWD_FUSED", "1") != "0"
 
 
 def igemm_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
@@ -527,6 +537,11 @@ def _use_vendor_wgrad(x: torch.Tensor, dy: torch.Tensor, w: torch.Tensor, stride
     return hit
 
 
+def _own_wgrad_decided(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int) -> bool:
+    """The weight-gradient tuner is off, or already chose the own kernel for this shape (no timing)."""
+    return not TUNE or _wgrad_plan.get((tuple(x.shape), tuple(w.shape), stride, pad)) is False
+
+
 def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, w: torch.Tensor, stride: int, pad: int, wparam=None):
     """Weight gradient.  Returns None when it was accumulated directly into the
     parameter's flat gradient buffer (and the bucket notified), else dW."""
@@ -553,6 +568,158 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, w: torch.Tensor, stride: int, 
     dw = torch.empty_like(w, memory_format=torch.channels_last)
     wgrad_into(x, dy, dw, Nb, H, W, Ci, P_, Q_, Co, R, S, stride, pad, accumulate=False)
     return dw
+
+
+class Conv3BwdLink:
+    """Hand-off between a bottleneck's conv3 and the bn3 that consumes its output, created in the
+    forward: bn3's backward leaves its input gradient dx3 UNWRITTEN and conv3's backward forms it
+    tile by tile inside ``kfa_conv3_bwd_fused`` (no dx3 tensor is written or re-read).
+
+    States: ``armed`` (conv3's forward made it and tagged its output) -> ``taken`` (bn3's forward
+    picked it up: training, ReLU with residual bits, not the dual form) -> ``deferred`` (bn3's
+    backward ran finalize only into ``coef`` and returned ``placeholder``) -> ``done``.  conv3's
+    backward runs the fused kernel iff its ``dy`` IS the placeholder and both gradients are wanted;
+    in every other case :meth:`materialize` first writes dx3 into the placeholder with the ordinary
+    apply pass, and the separate kernels run as before.  Only a conv whose output feeds that BN
+    alone may be armed (the model asks for it: ``conv2d(..., tail_link=True)``)."""
+
+    __slots__ = ("state", "g", "x3", "mb", "coef", "placeholder", "relu")
+
+    def __init__(self):
+        self.state = "armed"
+        self.g = self.x3 = self.mb = self.coef = self.placeholder = None
+        self.relu = True
+
+    def take(self) -> bool:
+        """bn3's forward: True once, for an armed link."""
+        if self.state != "armed":
+            return False
+        self.state = "taken"
+        return True
+
+    def defer(self, g, x3, mb, coef, placeholder, relu=True) -> None:
+        """bn3's backward: dx3 = coef . (g * mb, x3, 1) is left to conv3's backward."""
+        if self.state != "taken":
+            raise RuntimeError(f"Conv3BwdLink.defer in state {self.state!r}")
+        self.g, self.x3, self.mb, self.coef, self.placeholder, self.relu = g, x3, mb, coef, placeholder, relu
+        self.state = "deferred"
+
+    def is_placeholder(self, dy) -> bool:
+        ph = self.placeholder
+        return (self.state == "deferred" and ph is not None and dy is not None and dy.data_ptr() == ph.data_ptr()
+                and dy.shape == ph.shape and dy.stride() == ph.stride() and dy.dtype == ph.dtype)
+
+    def materialize(self) -> None:
+        """The fallback: write dx3 into the placeholder with bn3's ordinary apply pass."""
+        if self.state != "deferred":
+            return
+        C = self.x3.shape[1] if self.x3.dim() == 4 else self.x3.shape[-1]
+        _lib.call("kfa_bn_bwd_apply_only", _lib.ptr(self.g), _lib.ptr(self.x3), None, _lib.ptr(self.coef),
+                  _lib.ptr(self.placeholder), self.x3.numel() // C, C, int(self.relu), None, _lib.ptr(self.mb),
+                  _lib.stream())
+        self.clear()
+
+    def clear(self) -> None:
+        self.g = self.x3 = self.mb = self.coef = self.placeholder = None
+        self.state = "done"
+
+
+def conv3_bwd_shape_ok(x_shape, w_shape, stride: int, pad: int) -> bool:
+    """Shapes ``kfa_conv3_bwd_fused`` covers: 1x1 / stride 1 / pad 0, Ci = 64 / 128, Co = 4 Ci, 32-bit offsets."""
+    Nb, Ci, H, W = x_shape
+    Co, _, R, S = w_shape
+    K = Nb * H * W
+    return (R == 1 and S == 1 and stride == 1 and pad == 0 and Ci in (64, 128) and Co == 4 * Ci and 0 < K < (1 << 24)
+            and K * Co * 2 < (1 << 31))
+
+
+def conv3_bwd_fused(g, x3, mb, coef, y2, w, grad, accumulate: bool, bn=None, max_blocks: int = 0,
+                    stride: int = 1, pad: int = 0) -> torch.Tensor:
+    """``kfa_conv3_bwd_fused``: returns dX2; ``grad`` ([Co][1][1][Ci] memory, bf16 / fp32) (+)= dW.
+    ``bn``: the ``BnBwdLink`` of the BatchNorm whose output ``y2`` is (its backward statistics)."""
+    Nb, Ci, H, W = y2.shape
+    Co, _, R, S = w.shape
+    dx = torch.empty((Nb, Ci, H, W), dtype=y2.dtype, device=y2.device, memory_format=torch.channels_last)
+    wt = _transposed_weight(_cl(w), 0, 1, R, 0, 1, S)
+    nfl = _lib.lib().kfa_conv3_bwd_part_floats(Nb, H, W, Co, Ci, max_blocks)
+    part = _lib.workspace(max(nfl, 1) * 4, y2.device, f"conv3_bwd_part{_lib.stream() or 0}").view(torch.float32)
+    bn_ws = None
+    bn_x = bn_mean = bn_ss = bn_mb = None
+    relu = 0
+    if bn is not None:
+        from .batchnorm import bn_slot_workspace
+        bn_ws = bn_slot_workspace(Ci, y2.device)
+        bn_x, bn_mean, bn_ss, bn_mb, relu = bn.x, bn.mean, bn.ss, bn.mb, int(bn.relu)
+    _lib.call("kfa_conv3_bwd_fused", _lib.ptr(g), _lib.ptr(x3), _lib.ptr(mb), _lib.ptr(coef), _lib.ptr(y2),
+              _lib.ptr(wt), _lib.ptr(dx), _lib.ptr(grad), int(grad.dtype == torch.float32), int(accumulate),
+              _lib.ptr(part), Nb, H, W, Ci, Co, R, S, stride, pad, _lib.ptr(bn_ws), _lib.ptr(bn_x), _lib.ptr(bn_mean),
+              relu, _lib.ptr(bn_ss), _lib.ptr(bn_mb), max_blocks, _lib.stream())
+    if bn is not None:
+        bn.prestats = True
+    return dx
+
+
+def conv3_bwd_candidates(Nb: int, H: int, W: int, Ci: int, Co: int, device) -> tuple:
+    """``([("sep", fn), ("fused", fn)], clean)`` on scratch operands of one shape: bn3's apply pass +
+    conv3's dgrad (with bn2's backward statistics) + wgrad + reduce, against the one-pass kernel;
+    ``clean()`` zeroes the BatchNorm slots the launches filled.  What the ``conv3_bwd`` route times
+    when the shape is not in the table, and ``tools/bench_conv3_bwd.py``."""
+    cl = torch.channels_last
+    bf = dict(dtype=torch.bfloat16, device=device)
+    g = torch.randn(Nb, Co, H, W, **bf).contiguous(memory_format=cl)
+    x3 = torch.randn(Nb, Co, H, W, **bf).contiguous(memory_format=cl)
+    y2 = torch.randn(Nb, Ci, H, W, **bf).contiguous(memory_format=cl)
+    w = (torch.randn(Co, Ci, 1, 1, **bf) * 0.05).contiguous(memory_format=cl)
+    mb = torch.randint(0, 256, (Nb * H * W * Co // 8,), dtype=torch.uint8, device=device)
+    coef = torch.randn(3 * Co, dtype=torch.float32, device=device) * 0.1
+    dx3 = torch.empty_like(x3)
+    acc = torch.zeros(w.shape, dtype=torch.float32, device=device).contiguous(memory_format=cl)
+    from .batchnorm import BnBwdLink
+    bn = BnBwdLink()
+    bn.x = torch.randn(Nb, Ci, H, W, **bf).contiguous(memory_format=cl)
+    bn.mean = torch.zeros(Ci, dtype=torch.float32, device=device)
+    bn.ss = torch.ones(2 * Ci, dtype=torch.float32, device=device)
+    bn.relu = True
+    M = Nb * H * W
+
+    def clean():  # the timed launches fill the shared slot workspace: leave it zeroed
+        from .batchnorm import bn_slot_workspace
+        bn_slot_workspace(Ci, device).zero_()
+        bn.prestats = False
+
+    def sep():
+        _lib.call("kfa_bn_bwd_apply_only", _lib.ptr(g), _lib.ptr(x3), None, _lib.ptr(coef), _lib.ptr(dx3), M, Co, 1,
+                  None, _lib.ptr(mb), _lib.stream())
+        conv_dgrad(dx3, w, y2.shape, 1, 0, None, bn)
+        wgrad_into(y2, dx3, acc, Nb, H, W, Ci, H, W, Co, 1, 1, 1, 0, True)
+
+    def fused():
+        conv3_bwd_fused(g, x3, mb, coef, y2, w, acc, True, bn)
+
+    return [("sep", sep), ("fused", fused)], clean
+
+
+def _conv3_bwd_route(x_shape, w_shape, device) -> bool:
+    """The ``conv3_bwd`` decision of one shape: ``fused`` against ``sep`` (the default form; the
+    fused kernel must beat it by the usual margin).  From the committed table, else timed once."""
+    from . import routes
+    Nb, Ci, H, W = x_shape
+    Co = w_shape[0]
+    key = (Nb, H, W, Ci, Co)
+    made = None  # the scratch operands exist only if the shape has to be timed
+
+    def lazy(i):
+        def run():
+            nonlocal made
+            if made is None:
+                made = conv3_bwd_candidates(Nb, H, W, Ci, Co, device)
+            made[0][i][1]()
+        return run
+
+    pick = routes.decide("conv3_bwd", key, device, [("sep", lazy(0)), ("fused", lazy(1))])
+    if made is not None:
+        made[1]()
+    return pick == 1
 
 
 class GradJoin:
@@ -654,9 +821,10 @@ def _use_bnpro(lz, x, w, stride, pad, stats) -> bool:
 
 class _ConvFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, stride, pad, join, stats, vendor=False, lazy=None):
+    def forward(ctx, x, w, stride, pad, join, stats, vendor=False, lazy=None, tail=None):
         ctx.save_for_backward(x, w)
         ctx.stride, ctx.pad, ctx.join = stride, pad, join
+        ctx.tail = tail  # Conv3BwdLink: the consuming BatchNorm's backward may leave dy unwritten
         ctx.wparam = w  # the Parameter itself (for the direct flat-gradient write)
         ctx.bn_link = getattr(x, "_kfa_bn_link", None)  # x = output of a BatchNorm (see conv_dgrad)
         if ctx.bn_link is not None:
@@ -673,6 +841,17 @@ class _ConvFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
         dx = dw = None
+        tail = ctx.tail
+        if tail is not None and tail.state == "deferred":
+            # (dy is unwritten here: the vendor-wgrad tuner is only asked for a decision it already
+            # made, never run; the BatchNorm link must carry a mask the fused entry takes)
+            bn = ctx.bn_link
+            if (tail.is_placeholder(dy) and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and CONV3_BWD_FUSED
+                    and ctx.join is None and not WGRAD_SIDE and wgrad_ok(x, dy, w)
+                    and _own_wgrad_decided(x, w, ctx.stride, ctx.pad)
+                    and (bn is None or bn.convs != 1 or bn.y is None)):
+                return _ConvFn._backward_fused(ctx, tail, x, w)
+            tail.materialize()  # dx3 into the placeholder (dy, unless dy is a foreign tensor), then as ever
         if ctx.needs_input_grad[0]:
             addend = addend_mask = None
             bn_link = ctx.bn_link if (ctx.bn_link is not None and ctx.bn_link.convs == 1) else None
@@ -702,7 +881,23 @@ class _ConvFn(torch.autograd.Function):
                     torch.cuda.current_stream(x.device).wait_stream(_streams.side_stream(x.device))
             else:
                 dw = conv_wgrad(x, dy, w, ctx.stride, ctx.pad, ctx.wparam)
-        return dx, dw, None, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None, None
+
+    @staticmethod
+    def _backward_fused(ctx, tail, x, w):
+        """bn3's apply + this conv's dgrad + wgrad in one pass over g and x3 (``Conv3BwdLink``)."""
+        bn_link = ctx.bn_link if (ctx.bn_link is not None and ctx.bn_link.convs == 1) else None
+        wparam = ctx.wparam
+        target = direct_grad_view(wparam) if wparam is not None else None
+        direct = target is not None and target.dtype in (torch.bfloat16, torch.float32) and \
+            target.is_contiguous(memory_format=torch.channels_last)
+        grad = target if direct else torch.empty_like(w, memory_format=torch.channels_last)
+        dx = conv3_bwd_fused(tail.g, tail.x3, tail.mb, tail.coef, _cl(x), w, grad, direct, bn_link,
+                             stride=ctx.stride, pad=ctx.pad)
+        tail.clear()
+        if direct:
+            notify_grad_ready(wparam)
+        return dx, (None if direct else grad), None, None, None, None, None, None, None
 
 
 def apply_bit_mask(t: torch.Tensor, bits: torch.Tensor) -> torch.Tensor:
@@ -780,13 +975,17 @@ class _StemConvFn(torch.autograd.Function):
         return dx, dw, None, None, None
 
 
-def conv2d(x, w, stride: int = 1, pad: int = 0, join: "GradJoin | None" = None, bn_stats=False):
+def conv2d(x, w, stride: int = 1, pad: int = 0, join: "GradJoin | None" = None, bn_stats=False,
+           tail_link: bool = False):
     """``bn_stats``: the caller guarantees a training-mode ``BatchNorm2dAct``
     consumes the output next; the epilogue then accumulates its statistics and
     the output is tagged ``_kfa_prestats`` (the BN skips its stats pass).  A
     string names the slot workspace (``ops.batchnorm.bn_slot_workspace`` tag)
     for a BN whose finalize runs later than the next BN's (the downsample BN of
-    ``bn_act_dual``); True = the shared one."""
+    ``bn_act_dual``); True = the shared one.  ``tail_link``: the caller guarantees the output
+    feeds one training ``BatchNorm2dAct`` (+ residual + ReLU) and nothing else; for a shape the
+    one-pass backward covers and the ``conv3_bwd`` route picks, the output is tagged with an
+    armed ``Conv3BwdLink``."""
     tag = bn_stats if isinstance(bn_stats, str) else "bn_slots"
 
     def slots():  # the BN's slot workspace (fetched only on a path whose epilogue fills it)
@@ -795,17 +994,26 @@ def conv2d(x, w, stride: int = 1, pad: int = 0, join: "GradJoin | None" = None, 
         from .batchnorm import bn_slot_workspace
         return bn_slot_workspace(w.shape[0], x.device, tag)
 
-    def tagged(y, stats):
+    def tagged(y, stats, tail=None):
         if stats is not None:
             y._kfa_prestats = True
             y._kfa_prestats_tag = tag
+        if tail is not None:
+            y._kfa_conv3_link = tail
         return y
+
+    def armed():  # a Conv3BwdLink for this conv's backward, or None
+        if not (tail_link and CONV3_BWD_FUSED and join is None and torch.is_grad_enabled() and x.is_cuda
+                and conv3_bwd_shape_ok(tuple(x.shape), tuple(w.shape), stride, pad)):
+            return None
+        return Conv3BwdLink() if _conv3_bwd_route(tuple(x.shape), tuple(w.shape), x.device) else None
 
     lz = getattr(x, "_kfa_lazy", None)
     if lz is not None and lz.pending and join is None and igemm_ok(x, w):
         stats = slots()
         if _use_bnpro(lz, x, w, stride, pad, stats):
-            return tagged(_ConvFn.apply(x, w, stride, pad, None, stats, False, lz), stats)
+            tail = armed()
+            return tagged(_ConvFn.apply(x, w, stride, pad, None, stats, False, lz, tail), stats, tail)
     if lz is not None and lz.pending:
         from .batchnorm import materialize
         materialize(x)
@@ -819,7 +1027,8 @@ def conv2d(x, w, stride: int = 1, pad: int = 0, join: "GradJoin | None" = None, 
         vendor = _use_vendor_fwd(x, w, stride, pad, stats)
         if vendor:
             stats = None  # the BN runs its own statistics pass
-        return tagged(_ConvFn.apply(x, w, stride, pad, join, stats, vendor), stats)
+        tail = None if vendor else armed()
+        return tagged(_ConvFn.apply(x, w, stride, pad, join, stats, vendor, None, tail), stats, tail)
     return F.conv2d(x, w, None, stride, pad)  # unfused: join.branch() is a no-op alias
 
 
@@ -837,9 +1046,10 @@ class Conv2d(nn.Module):
         self.weight = nn.Parameter(w.contiguous(memory_format=torch.channels_last))
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
 
-    def forward(self, x, join: "GradJoin | None" = None, bn_stats=False):
+    def forward(self, x, join: "GradJoin | None" = None, bn_stats=False, tail_link: bool = False):
         w = self.weight if self.weight.dtype == x.dtype else self.weight.to(x.dtype)
-        y = conv2d(x, w, self.stride, self.padding, join, bn_stats if self.bias is None else False)
+        y = conv2d(x, w, self.stride, self.padding, join, bn_stats if self.bias is None else False,
+                   tail_link and self.bias is None)
         if self.bias is not None:
             y = y + self.bias.to(y.dtype).view(1, -1, 1, 1)
         return y

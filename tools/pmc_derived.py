@@ -13,6 +13,10 @@ On MI355X (8 XCDs x 32 CUs x 4 SIMDs) the derived columns are:
 * LDS conflict = SQ_LDS_BANK_CONFLICT / SQ_ACTIVE_INST_LDS (extra LDS cycles per LDS-busy cycle);
 * LDS-wait share = SQ_WAIT_INST_LDS / SQ_WAVE_CYCLES;
 * HBM read / write = FETCH_SIZE / WRITE_SIZE (KiB counters) per dispatch, and their sum over time.
+  On gfx950 FETCH_SIZE reports exactly half the bytes of a wide coalesced read (16 B per lane,
+  global loads and LDS-DMA alike: 128-B requests tallied at 64 B), so "HBM read MB" under-counts
+  streaming kernels 2x; "read x2 MB" / "TB/s (read x2)" show the doubled figure, the one to set
+  against a byte count or the ~6.3 TB/s achievable (an upper bound for kernels with narrow reads).
 """
 import collections
 import csv
@@ -47,8 +51,8 @@ def main(paths, keep=("gemm", "wgrad", "conv", "seg_", "radix", "scan_max", "bn_
                       "maxpool", "pool", "stem", "sgd", "adam", "xent", "gap_")):
     rows = load(paths)
     print("| kernel | dispatches | mean us | MFMA busy | MFMA TF/s | LDS conflict | LDS-wait share | "
-          "HBM read MB | HBM write MB | HBM TB/s |")
-    print("|---|---:|---:|---:|---:|---:|---:|---:|---:|---:|")
+          "HBM read MB | HBM write MB | HBM TB/s | read x2 MB | TB/s (read x2) |")
+    print("|---|---:|---:|---:|---:|---:|---:|---:|---:|---:|---:|---:|")
     for k, m in sorted(rows.items(), key=lambda kv: -kv[1]["_us"] * kv[1]["_n"]):
         if not any(s in k for s in keep):
             continue
@@ -65,9 +69,11 @@ def main(paths, keep=("gemm", "wgrad", "conv", "seg_", "radix", "scan_max", "bn_
         wr = m["WRITE_SIZE"] / 1024 if "WRITE_SIZE" in m else None
         bw = (rd or 0) + (wr or 0)
         tbs = bw * 1e6 / (us * 1e-6) / 1e12 if rd is not None or wr is not None else None
+        rd2 = 2 * rd if rd is not None else None  # gfx950: FETCH_SIZE halves wide reads (see the docstring)
+        tbs2 = (2 * (rd or 0) + (wr or 0)) * 1e6 / (us * 1e-6) / 1e12 if tbs is not None else None
         print(f"| `{k}` | {m['_n']} | {us:.1f} | {fmt(mb and mb * 100, '.0f')}% | {fmt(tf, '.0f')} | "
               f"{fmt(conf and conf * 100, '.0f')}% | {fmt(wl and wl * 100, '.1f')}% | {fmt(rd, '.1f')} | "
-              f"{fmt(wr, '.1f')} | {fmt(tbs, '.2f')} |")
+              f"{fmt(wr, '.1f')} | {fmt(tbs, '.2f')} | {fmt(rd2, '.1f')} | {fmt(tbs2, '.2f')} |")
 
 
 def issue(paths, keep=("attn", "gemm", "wgrad", "conv", "ln_", "bias_act")):
