@@ -5,7 +5,9 @@
 // tensor.  Mixed precision: the fp32 master copy is updated and the bf16
 // compute copy (if any) is rewritten in the same pass; grads may be bf16
 // (the all-reduced bucket) or fp32.  8 elements per lane, 16-B loads for
-// bf16, 2x16-B for fp32.
+// bf16, 2x16-B for fp32.  LAMB and the global-norm clip coefficient (further down) add
+// per-tensor and whole-gradient norms as fixed-order segmented reductions over the same
+// buffers; every scalar they produce stays in device memory.
 #include "common.h"
 
 namespace {
@@ -66,6 +68,30 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ w, bf16_t*
 }
 
 // AdamW (decoupled weight decay; wd = 0 gives Adam).  bc1 = 1 - b1^t, bc2 = 1 - b2^t.
+// One 8-element vector at element i: the body of adam_kernel and adam_clip_kernel.
+template <bool GBF16>
+__device__ __forceinline__ void adam_vec8(float* __restrict__ w, bf16_t* __restrict__ wb,
+                                          const void* __restrict__ g, float* __restrict__ m_,
+                                          float* __restrict__ v_, long i, float lr, float b1, float b2, float eps,
+                                          float wd, float step, float rbc2, float gscale) {
+  float gr[8], p[8], m[8], s[8];
+  load_grad8<GBF16>(g, i, gr, gscale);
+  load8(w + i, p);
+  load8(m_ + i, m);
+  load8(v_ + i, s);
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    m[j] = fmaf(b1, m[j], (1.f - b1) * gr[j]);
+    s[j] = fmaf(b2, s[j], (1.f - b2) * gr[j] * gr[j]);
+    const float denom = sqrtf(s[j]) * rbc2 + eps;
+    p[j] = p[j] * (1.f - lr * wd) - step * m[j] / denom;
+  }
+  store8(m_ + i, m);
+  store8(v_ + i, s);
+  store8(w + i, p);
+  if (wb) *reinterpret_cast<uint4*>(wb + i) = pack8(p);
+}
+
 template <bool GBF16>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, bf16_t* __restrict__ wb,
                                                    const void* __restrict__ g, float* __restrict__ m_,
@@ -78,25 +104,25 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, bf16_t
   }
   const float step = lr / bc1;
   const float rbc2 = rsqrtf(bc2);
-  for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < n8; v += (long)gridDim.x * blockDim.x) {
-    const long i = v * 8;
-    float gr[8], p[8], m[8], s[8];
-    load_grad8<GBF16>(g, i, gr, gscale);
-    load8(w + i, p);
-    load8(m_ + i, m);
-    load8(v_ + i, s);
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      m[j] = fmaf(b1, m[j], (1.f - b1) * gr[j]);
-      s[j] = fmaf(b2, s[j], (1.f - b2) * gr[j] * gr[j]);
-      const float denom = sqrtf(s[j]) * rbc2 + eps;
-      p[j] = p[j] * (1.f - lr * wd) - step * m[j] / denom;
-    }
-    store8(m_ + i, m);
-    store8(v_ + i, s);
-    store8(w + i, p);
-    if (wb) *reinterpret_cast<uint4*>(wb + i) = pack8(p);
-  }
+  for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < n8; v += (long)gridDim.x * blockDim.x)
+    adam_vec8<GBF16>(w, wb, g, m_, v_, v * 8, lr, b1, b2, eps, wd, step, rbc2, gscale);
+}
+
+// The same step with the gradient scale multiplied by a device scalar: the global-norm
+// clip coefficient clip_finish_kernel wrote earlier in this step.  It is exactly 1.0f
+// when the norm is under the threshold, and the step is then adam_kernel's bit for bit.
+template <bool GBF16>
+__global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ w, bf16_t* __restrict__ wb,
+                                                        const void* __restrict__ g, float* __restrict__ m_,
+                                                        float* __restrict__ v_, long n8, float lr, float b1,
+                                                        float b2, float eps, float wd, float gscale,
+                                                        const float* __restrict__ dbc,
+                                                        const float* __restrict__ dcoef) {
+  const float step = lr / dbc[0];
+  const float rbc2 = rsqrtf(dbc[1]);
+  gscale *= dcoef[0];
+  for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < n8; v += (long)gridDim.x * blockDim.x)
+    adam_vec8<GBF16>(w, wb, g, m_, v_, v * 8, lr, b1, b2, eps, wd, step, rbc2, gscale);
 }
 
 // t += 1; bc = (1 - b1^t, 1 - b2^t): the per-step scalars of Adam kept on the
@@ -137,6 +163,164 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const void* __restrict__ g, 
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(out, sh[0] + sh[1] + sh[2] + sh[3]);
 }
+
+// ---------------------------------------------------------------- LAMB + global-norm clipping
+// Norms are segmented reductions over the flat buffer in a FIXED order (no float atomics,
+// no zero-fill): the host cuts every tensor into chunks of at most CHUNK elements, a chunk
+// never crossing a tensor boundary, and keeps the table on the device as rows of three
+// longs (tensor id, start, length).  start is a multiple of 8 and the buffer is padded to
+// 8 past every tensor, so the last vector of a tensor may be loaded whole; its elements
+// at or past `length` are padding: they hold 0, take no part in a sum and are written
+// back unchanged.  One block reduces one chunk — lanes over vectors in address order,
+// the xor tree of wave_sum, the four waves in order — and stores its partial with a
+// plain store, so every step overwrites every partial.
+
+// block-wide sums of a and b in thread 0 (valid there only); fixed order
+__device__ __forceinline__ void block_sum2(float& a, float& b, float (*sh)[2]) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  __syncthreads();  // sh from the previous chunk has been read
+  if ((threadIdx.x & 63) == 0) {
+    sh[threadIdx.x >> 6][0] = a;
+    sh[threadIdx.x >> 6][1] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = ((sh[0][0] + sh[1][0]) + sh[2][0]) + sh[3][0];
+    b = ((sh[0][1] + sh[1][1]) + sh[2][1]) + sh[3][1];
+  }
+}
+
+// per-chunk sum of squares of the (unscaled) gradient: part[c]
+template <bool GBF16>
+__global__ __launch_bounds__(256) void chunk_sumsq_kernel(const void* __restrict__ g, const long* __restrict__ chunks,
+                                                          int nchunks, float* __restrict__ part) {
+  __shared__ float sh[4][2];
+  for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const long start = chunks[3 * c + 1], len = chunks[3 * c + 2];
+    float acc = 0.f, unused = 0.f;
+    for (long o = (long)threadIdx.x * 8; o < len; o += 256 * 8) {
+      float gr[8];
+      load_grad8<GBF16>(g, start + o, gr, 1.f);
+      const long valid = len - o;
+#pragma unroll
+      for (int j = 0; j < 8; j++) acc = j < valid ? fmaf(gr[j], gr[j], acc) : acc;
+    }
+    block_sum2(acc, unused, sh);
+    if (threadIdx.x == 0) part[c] = acc;
+  }
+}
+
+// out[0] = norm = gscale * sqrt(sum of every partial), out[1] = min(1, max_norm / (norm + 1e-6)):
+// torch.nn.utils.clip_grad_norm_'s coefficient.  One wave: lane l sums partials l, l + 64, ...
+// in order, then the xor tree; lane 0 writes.
+__global__ __launch_bounds__(64) void clip_finish_kernel(const float* __restrict__ part, int nparts, float gscale,
+                                                         float max_norm, float* __restrict__ out) {
+  float acc = 0.f;
+  for (int k = threadIdx.x; k < nparts; k += 64) acc += part[k];
+  acc = wave_sum(acc);
+  if (threadIdx.x == 0) {
+    const float norm = gscale * sqrtf(acc);
+    out[0] = norm;
+    out[1] = fminf(1.f, max_norm / (norm + 1e-6f));
+  }
+}
+
+// u = (m / bc1) / (sqrt(v / bc2) + eps) + wd * w with rbc1 = 1 / bc1, rbc2 = rsqrt(bc2):
+// stage 1 takes its norm and stage 2 recomputes it from the stored m, v, w by this one expression
+__device__ __forceinline__ float lamb_u(float m, float v, float w, float rbc1, float rbc2, float eps, float wd) {
+  return fmaf(wd, w, (m * rbc1) / fmaf(sqrtf(v), rbc2, eps));
+}
+
+// Stage 1: the Adam moments from g * gscale * dcoef, and per chunk the partial sums of
+// w^2 and u^2: part[2c], part[2c + 1] (part == nullptr: a space that takes r = 1).
+template <bool GBF16>
+__global__ __launch_bounds__(256) void lamb_stage1_kernel(const float* __restrict__ w, const void* __restrict__ g,
+                                                          float* __restrict__ m_, float* __restrict__ v_,
+                                                          const long* __restrict__ chunks, int nchunks,
+                                                          float* __restrict__ part, float b1, float b2, float eps,
+                                                          float wd, float gscale, const float* __restrict__ dbc,
+                                                          const float* __restrict__ dcoef) {
+  __shared__ float sh[4][2];
+  const float rbc1 = 1.f / dbc[0];
+  const float rbc2 = rsqrtf(dbc[1]);
+  if (dcoef) gscale *= dcoef[0];
+  for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const long start = chunks[3 * c + 1], len = chunks[3 * c + 2];
+    float sw = 0.f, su = 0.f;
+    for (long o = (long)threadIdx.x * 8; o < len; o += 256 * 8) {
+      const long i = start + o, valid = len - o;
+      float gr[8], p[8], m[8], s[8];
+      load_grad8<GBF16>(g, i, gr, gscale);
+      load8(w + i, p);
+      load8(m_ + i, m);
+      load8(v_ + i, s);
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        if (j < valid) {
+          m[j] = fmaf(b1, m[j], (1.f - b1) * gr[j]);
+          s[j] = fmaf(b2, s[j], (1.f - b2) * gr[j] * gr[j]);
+          const float u = lamb_u(m[j], s[j], p[j], rbc1, rbc2, eps, wd);
+          sw = fmaf(p[j], p[j], sw);
+          su = fmaf(u, u, su);
+        }
+      }
+      store8(m_ + i, m);
+      store8(v_ + i, s);
+    }
+    if (part) {
+      block_sum2(sw, su, sh);
+      if (threadIdx.x == 0) {
+        part[2 * c] = sw;
+        part[2 * c + 1] = su;
+      }
+    }
+  }
+}
+
+// ratio[t] = |w_t| / |u_t| from the partials of tensor t's chunks [tens[2t], tens[2t] + tens[2t + 1]),
+// 1 when either norm is 0.  One wave per tensor: lane l sums chunks l, l + 64, ... in order, then the xor tree.
+__global__ __launch_bounds__(64) void lamb_ratio_kernel(const float* __restrict__ part, const long* __restrict__ tens,
+                                                        float* __restrict__ ratio) {
+  const long first = tens[2 * blockIdx.x], count = tens[2 * blockIdx.x + 1];
+  float sw = 0.f, su = 0.f;
+  for (long k = threadIdx.x; k < count; k += 64) {
+    sw += part[2 * (first + k)];
+    su += part[2 * (first + k) + 1];
+  }
+  sw = wave_sum(sw);
+  su = wave_sum(su);
+  if (threadIdx.x == 0) ratio[blockIdx.x] = (sw > 0.f && su > 0.f) ? sqrtf(sw) / sqrtf(su) : 1.f;
+}
+
+// Stage 2: w -= lr * r_t * u, u recomputed from the stored m, v and the still un-updated w
+// (no per-element scratch); the bf16 compute copy rewritten from w.  ratio == nullptr: r = 1.
+__global__ __launch_bounds__(256) void lamb_stage2_kernel(float* __restrict__ w, bf16_t* __restrict__ wb,
+                                                          const float* __restrict__ m_, const float* __restrict__ v_,
+                                                          const long* __restrict__ chunks, int nchunks,
+                                                          const float* __restrict__ ratio, float lr, float eps,
+                                                          float wd, const float* __restrict__ dbc) {
+  const float rbc1 = 1.f / dbc[0];
+  const float rbc2 = rsqrtf(dbc[1]);
+  for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const long start = chunks[3 * c + 1], len = chunks[3 * c + 2];
+    const float step = ratio ? lr * ratio[chunks[3 * c]] : lr;
+    for (long o = (long)threadIdx.x * 8; o < len; o += 256 * 8) {
+      const long i = start + o, valid = len - o;
+      float p[8], m[8], s[8];
+      load8(w + i, p);
+      load8(m_ + i, m);
+      load8(v_ + i, s);
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        if (j < valid) p[j] = fmaf(-step, lamb_u(m[j], s[j], p[j], rbc1, rbc2, eps, wd), p[j]);
+      store8(w + i, p);
+      if (wb) *reinterpret_cast<uint4*>(wb + i) = pack8(p);
+    }
+  }
+}
+
+int chunk_grid(int nchunks) { return nchunks < 2048 ? nchunks : 2048; }
 
 int grid_for(long n8) {
   long b = (n8 + 255) / 256;
@@ -189,6 +373,72 @@ KFA_API int kfa_adam_bc_seed(int* t, float* bc, float b1, float b2, int seed, hi
 KFA_API int kfa_f32_to_bf16(const float* a, bf16_t* b, long n, hipStream_t s) {
   if (n % 8) return -1;
   hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for(n / 8)), dim3(256), 0, s, a, b, n / 8);
+  return kfa_status();
+}
+
+// kfa_adam_step with gscale * dcoef[0] as the gradient scale; dbc and dcoef are device scalars
+KFA_API int kfa_adam_step_clip(float* w, bf16_t* wb, const void* g, int g_is_bf16, float* m, float* v, long n,
+                               float lr, float b1, float b2, float eps, float wd, float gscale, const float* dbc,
+                               const float* dcoef, hipStream_t s) {
+  if (n % 8 || !dbc || !dcoef) return -1;
+  const long n8 = n / 8;
+  if (g_is_bf16)
+    hipLaunchKernelGGL(adam_clip_kernel<true>, dim3(grid_for(n8)), dim3(256), 0, s, w, wb, g, m, v, n8, lr, b1, b2,
+                       eps, wd, gscale, dbc, dcoef);
+  else
+    hipLaunchKernelGGL(adam_clip_kernel<false>, dim3(grid_for(n8)), dim3(256), 0, s, w, wb, g, m, v, n8, lr, b1, b2,
+                       eps, wd, gscale, dbc, dcoef);
+  return kfa_status();
+}
+
+// chunks: nchunks device rows of three longs: tensor id, start, length; start % 8 == 0, the buffers
+// readable up to the next multiple of 8 past start + length, length <= 65536.  part[nchunks].
+KFA_API int kfa_chunk_sumsq(const void* g, int g_is_bf16, const long* chunks, int nchunks, float* part,
+                            hipStream_t s) {
+  if (nchunks <= 0) return nchunks ? -1 : 0;
+  if (g_is_bf16)
+    hipLaunchKernelGGL(chunk_sumsq_kernel<true>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, g, chunks, nchunks, part);
+  else
+    hipLaunchKernelGGL(chunk_sumsq_kernel<false>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, g, chunks, nchunks, part);
+  return kfa_status();
+}
+
+// out[0] = gscale * sqrt of the sum of part[0..nparts), out[1] = the clip coefficient for max_norm
+KFA_API int kfa_clip_finish(const float* part, int nparts, float gscale, float max_norm, float* out,
+                            hipStream_t s) {
+  if (nparts < 0) return -1;
+  hipLaunchKernelGGL(clip_finish_kernel, dim3(1), dim3(64), 0, s, part, nparts, gscale, max_norm, out);
+  return kfa_status();
+}
+
+// LAMB stage 1: m, v updated; part[2 * nchunks] = per-chunk sums of w^2, u^2 or nullptr.
+// dbc: the device pair of kfa_adam_bc_seed; dcoef: nullptr or the device clip coefficient.
+KFA_API int kfa_lamb_stage1(const float* w, const void* g, int g_is_bf16, float* m, float* v, const long* chunks,
+                            int nchunks, float* part, float b1, float b2, float eps, float wd, float gscale,
+                            const float* dbc, const float* dcoef, hipStream_t s) {
+  if (nchunks <= 0 || !dbc) return nchunks ? -1 : 0;
+  if (g_is_bf16)
+    hipLaunchKernelGGL(lamb_stage1_kernel<true>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, g, m, v, chunks,
+                       nchunks, part, b1, b2, eps, wd, gscale, dbc, dcoef);
+  else
+    hipLaunchKernelGGL(lamb_stage1_kernel<false>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, g, m, v, chunks,
+                       nchunks, part, b1, b2, eps, wd, gscale, dbc, dcoef);
+  return kfa_status();
+}
+
+// tens: ntens device rows of two longs: first chunk, chunk count.  ratio[ntens].
+KFA_API int kfa_lamb_ratio(const float* part, const long* tens, int ntens, float* ratio, hipStream_t s) {
+  if (ntens <= 0) return ntens ? -1 : 0;
+  hipLaunchKernelGGL(lamb_ratio_kernel, dim3(ntens), dim3(64), 0, s, part, tens, ratio);
+  return kfa_status();
+}
+
+// LAMB stage 2: w (and wb, if any) updated with ratio[tensor id] (nullptr: 1) from the m, v of stage 1
+KFA_API int kfa_lamb_stage2(float* w, bf16_t* wb, const float* m, const float* v, const long* chunks, int nchunks,
+                            const float* ratio, float lr, float eps, float wd, const float* dbc, hipStream_t s) {
+  if (nchunks <= 0 || !dbc) return nchunks ? -1 : 0;
+  hipLaunchKernelGGL(lamb_stage2_kernel, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, wb, m, v, chunks, nchunks,
+                     ratio, lr, eps, wd, dbc);
   return kfa_status();
 }
 

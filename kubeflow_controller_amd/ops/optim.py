@@ -1,7 +1,10 @@
-"""Fused SGD(+momentum, weight decay, nesterov) and Adam/AdamW over flat
-parameter groups — ``csrc/kernels/optim.hip``.
+"""Fused SGD(+momentum, weight decay, nesterov), Adam/AdamW and LAMB over flat
+parameter groups, and global-norm gradient clipping for the latter two —
+``csrc/kernels/optim.hip``.
 
-One kernel launch per optimizer space per step; the gradient average over
+One kernel launch per optimizer space per step (LAMB: two passes and one small
+launch for its per-tensor trust ratios; clipping: one more read of the gradient,
+every norm and coefficient kept on the device); the gradient average over
 data-parallel ranks (``1/world``) and any loss scale are folded into
 ``grad_scale`` so no separate scaling pass runs.  A space is a whole flat group
 or the compact parameter-server / ZeRO shard a rank owns (``parallel/ps.py``):
@@ -25,6 +28,16 @@ _lib.register("kfa_adam_bc", [P, P, F, F, P])
 _lib.register("kfa_adam_bc_seed", [P, P, F, F, I, P])
 _lib.register("kfa_f32_to_bf16", [P, P, L, P])
 _lib.register("kfa_sumsq", [P, I, L, P, P])
+_lib.register("kfa_adam_step_clip", [P, P, P, I, P, P, L, F, F, F, F, F, F, P, P, P])
+_lib.register("kfa_chunk_sumsq", [P, I, P, I, P, P])
+_lib.register("kfa_clip_finish", [P, I, F, F, P, P])
+_lib.register("kfa_lamb_stage1", [P, P, I, P, P, P, I, P, F, F, F, F, F, P, P, P])
+_lib.register("kfa_lamb_ratio", [P, P, I, P, P])
+_lib.register("kfa_lamb_stage2", [P, P, P, P, P, I, P, F, F, F, P, P])
+
+# elements per chunk of the fixed-order segmented reductions (LAMB norms, the clip norm):
+# one block reduces one chunk, 8 vectors of 8 elements per lane (kfa_chunk_sumsq: <= 65536)
+CHUNK = 16384
 
 
 class OptSpace:
@@ -32,19 +45,26 @@ class OptSpace:
     weights ``w`` (updated in place), an optional low-precision compute copy
     ``wb`` rewritten from ``w`` in the same kernel, and the gradient ``grad``
     (bf16 or fp32).  A whole flat group (data-parallel all-reduce) or one
-    rank's compact shard of it (parameter-server / ZeRO owner, ``parallel/ps.py``)."""
+    rank's compact shard of it (parameter-server / ZeRO owner, ``parallel/ps.py``).
 
-    __slots__ = ("name", "w", "wb", "_grad")
+    ``segments``: the ``(start, numel)`` of every tensor in the region, for the
+    per-tensor norms of LAMB; ``None`` for the compact shards, whose cuts do not
+    follow tensor boundaries."""
 
-    def __init__(self, name: str, w: torch.Tensor, wb: Optional[torch.Tensor], grad):
+    __slots__ = ("name", "w", "wb", "_grad", "segments")
+
+    def __init__(self, name: str, w: torch.Tensor, wb: Optional[torch.Tensor], grad,
+                 segments: Optional[Sequence[Tuple[int, int]]] = None):
         self.name = name
         self.w = w
         self.wb = wb
         self._grad = grad
+        self.segments = [(int(a), int(n)) for a, n in segments] if segments is not None else None
 
     @classmethod
     def of_group(cls, g: FlatGroup) -> "OptSpace":
-        return cls(g.name, g.fp32, g.data if g.master is not None else None, lambda: g.opt_grad)
+        return cls(g.name, g.fp32, g.data if g.master is not None else None, lambda: g.opt_grad,
+                   segments=[(o, p.numel()) for o, p in zip(g.offsets, g.params)])
 
     @property
     def grad(self) -> torch.Tensor:
@@ -63,14 +83,51 @@ def _as_spaces(items) -> List[OptSpace]:
     return [x if isinstance(x, OptSpace) else OptSpace.of_group(x) for x in items]
 
 
+class _ChunkTable:
+    """The chunks of one space's tensors for the segmented reductions: ``chunks``
+    holds a row ``(tensor id, start, length)`` per chunk, a chunk never crossing a
+    tensor boundary, and ``tens`` a row ``(first chunk, chunk count)`` per tensor;
+    both int64, built once and kept on the space's device.  A space without
+    ``segments`` is one tensor.  The kernels load whole 8-element vectors, so
+    every segment must start on a multiple of 8 and leave the padding up to the
+    next multiple of 8 inside the buffer and outside every other segment."""
+
+    def __init__(self, s: OptSpace):
+        segs = s.segments if s.segments is not None else [(0, s.numel)]
+        rows, tens, end = [], [], 0
+        for t, (a, n) in enumerate(segs):
+            if a % 8 or n < 0 or a < end or -(-(a + n) // 8) * 8 > s.numel:
+                raise ValueError(f"optimizer space {s.name!r}: segment {t} = ({a}, {n}) is not an 8-aligned, "
+                                 f"ordered, padded cut of its {s.numel} elements")
+            end = a + n
+            first = len(rows)
+            rows += [(t, a + o, min(CHUNK, n - o)) for o in range(0, n, CHUNK)]
+            tens.append((first, len(rows) - first))
+        self.nchunks, self.ntens = len(rows), len(tens)
+        self.chunks = torch.tensor(rows, dtype=torch.int64, device=s.device).reshape(-1, 3)
+        self.tens = torch.tensor(tens, dtype=torch.int64, device=s.device).reshape(-1, 2)
+
+
 class _FusedBase:
     def __init__(self, spaces: Sequence, lr: float, weight_decay: float,
-                 decay_groups: Optional[Sequence[str]] = None):
+                 decay_groups: Optional[Sequence[str]] = None, max_grad_norm: Optional[float] = None):
         self.spaces: List[OptSpace] = _as_spaces(spaces)
         self.lr = lr
         self.weight_decay = weight_decay
         self.decay_groups = set(decay_groups) if decay_groups is not None else {"weights"}
         self.step_count = 0
+        self._tabs: Optional[List[_ChunkTable]] = None
+        # global-norm clipping: (pre-clip norm, coefficient) stay on the device; the step
+        # kernels read the coefficient there, so no step waits for the host
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._clip: Optional[torch.Tensor] = None
+        if self.max_grad_norm is not None:
+            if not self.max_grad_norm > 0:
+                raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm!r}")
+            dev = self.spaces[0].device if self.spaces else torch.device("cpu")
+            self._clip = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
+            if dev.type == "cuda":  # one partial per chunk, every space's in one buffer
+                self._gpart = torch.zeros(sum(t.nchunks for t in self._tables()), dtype=torch.float32, device=dev)
 
     def _wd(self, s: OptSpace) -> float:
         return self.weight_decay if s.name in self.decay_groups or not s.name else 0.0
@@ -78,6 +135,53 @@ class _FusedBase:
     @staticmethod
     def _cpu(s: OptSpace) -> bool:
         return not s.w.is_cuda
+
+    def _tables(self) -> List[_ChunkTable]:
+        if self._tabs is None:
+            self._tabs = [_ChunkTable(s) for s in self.spaces]
+        return self._tabs
+
+    def scratch_bytes(self) -> int:
+        """Bytes of the norm reductions' tables and partial sums: per chunk and per
+        tensor, never per element (0 without LAMB or clipping)."""
+        bufs = [self._clip, getattr(self, "_gpart", None), *getattr(self, "_part", []), *getattr(self, "_ratio", [])]
+        for t in self._tabs or []:
+            bufs += [t.chunks, t.tens]
+        return sum(b.numel() * b.element_size() for b in bufs if b is not None)
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        """The gradient's global L2 norm before clipping, as of the last step: a 0-d
+        tensor on the optimizer's device (``None`` without ``max_grad_norm``).  For
+        logging: reading it waits for the device, so the caller decides when."""
+        return self._clip[0] if self._clip is not None else None
+
+    @torch.no_grad()
+    def _clip_scalar(self, grad_scale: float) -> None:
+        """norm = grad_scale * |g| over every space and coef = min(1, max / (norm + 1e-6))
+        (``torch.nn.utils.clip_grad_norm_``) into ``_clip``, in a fixed summation order."""
+        if self._clip.is_cuda:
+            off = 0
+            for s, t in zip(self.spaces, self._tables()):
+                g = s.grad
+                _lib.call("kfa_chunk_sumsq", _lib.ptr(g), int(g.dtype == torch.bfloat16), _lib.ptr(t.chunks),
+                          t.nchunks, self._gpart.data_ptr() + 4 * off, _lib.stream())
+                off += t.nchunks
+            _lib.call("kfa_clip_finish", _lib.ptr(self._gpart), off, grad_scale, self.max_grad_norm,
+                      _lib.ptr(self._clip), _lib.stream())
+            return
+        total = torch.zeros((), dtype=torch.float32)
+        for s in self.spaces:
+            g = s.grad
+            for a, n in (s.segments if s.segments is not None else [(0, s.numel)]):
+                total += g[a:a + n].float().pow(2).sum()
+        norm = total.sqrt() * grad_scale
+        self._clip[0] = norm
+        self._clip[1] = (self.max_grad_norm / (norm + 1e-6)).clamp(max=1.0)
+
+    def _dcoef(self) -> Optional[int]:
+        """Device address of the clip coefficient (None: no clipping)."""
+        return self._clip.data_ptr() + 4 if self._clip is not None else None
 
     def grad_norm(self, grad_scale: float = 1.0) -> torch.Tensor:
         """L2 norm of the gradient this rank holds (its shard in the sharded layouts)."""
@@ -96,7 +200,10 @@ class _FusedBase:
 
 class FusedSGD(_FusedBase):
     def __init__(self, groups, lr=0.1, momentum=0.9, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 decay_groups=None):
+                 decay_groups=None, max_grad_norm=None):
+        if max_grad_norm is not None:
+            raise ValueError("FusedSGD: global-norm gradient clipping (max_grad_norm) is not built for SGD; "
+                             "use FusedAdam or FusedLAMB")
         super().__init__(groups, lr, weight_decay, decay_groups)
         self.momentum = momentum
         self.dampening = dampening
@@ -143,9 +250,12 @@ class FusedSGD(_FusedBase):
             self.update(si, 0, s.numel, grad_scale, lr)
 
 
-class FusedAdam(_FusedBase):
-    def __init__(self, groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decay_groups=None):
-        super().__init__(groups, lr, weight_decay, decay_groups)
+class _AdamMoments(_FusedBase):
+    """The state Adam and LAMB share: the moments ``m`` / ``v`` (the names
+    ``trainer/checkpoint.py`` saves) and the device step count / bias corrections."""
+
+    def __init__(self, groups, lr, betas, eps, weight_decay, decay_groups, max_grad_norm):
+        super().__init__(groups, lr, weight_decay, decay_groups, max_grad_norm)
         self.b1, self.b2 = betas
         self.eps = eps
         self.m = [torch.zeros(s.numel, dtype=torch.float32, device=s.device) for s in self.spaces]
@@ -167,6 +277,17 @@ class FusedAdam(_FusedBase):
                       _lib.stream())
         self.step_count += 1
 
+
+class FusedAdam(_AdamMoments):
+    """``max_grad_norm``: clip the gradient to that global L2 norm first, as
+    ``torch.nn.utils.clip_grad_norm_`` does.  ``step`` computes the coefficient on
+    the device and the update kernel reads it there; the ranged ``update`` applies
+    the coefficient of the last ``step``, so a clipped optimizer is stepped whole."""
+
+    def __init__(self, groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decay_groups=None,
+                 max_grad_norm=None):
+        super().__init__(groups, lr, betas, eps, weight_decay, decay_groups, max_grad_norm)
+
     @torch.no_grad()
     def update(self, si: int, a: int, b: int, grad_scale: float = 1.0, lr: Optional[float] = None) -> None:
         """Elements [a, b) of space ``si`` in the step opened by ``begin_step`` (elementwise:
@@ -183,12 +304,19 @@ class FusedAdam(_FusedBase):
         wd = self._wd(s)
         if self._cpu(s):
             d = gr.float() * grad_scale
+            if self._clip is not None:
+                d = d * self._clip[1]
             m.mul_(self.b1).add_(d, alpha=1 - self.b1)
             v.mul_(self.b2).addcmul_(d, d, value=1 - self.b2)
             denom = (v.sqrt() / math.sqrt(bc2)).add_(self.eps)
             w.mul_(1 - lr * wd).addcdiv_(m, denom, value=-lr / bc1)
             if wb is not None:
                 wb.copy_(w)
+            return
+        if self._clip is not None:
+            _lib.call("kfa_adam_step_clip", _lib.ptr(w), _lib.ptr(wb), _lib.ptr(gr), int(gr.dtype == torch.bfloat16),
+                      _lib.ptr(m), _lib.ptr(v), b - a, lr, self.b1, self.b2, self.eps, wd, grad_scale,
+                      _lib.ptr(self._bc), self._dcoef(), _lib.stream())
             return
         _lib.call("kfa_adam_step", _lib.ptr(w), _lib.ptr(wb), _lib.ptr(gr), int(gr.dtype == torch.bfloat16),
                   _lib.ptr(m), _lib.ptr(v), b - a, lr, self.b1, self.b2, self.eps, wd, bc1, bc2, grad_scale,
@@ -197,5 +325,85 @@ class FusedAdam(_FusedBase):
     @torch.no_grad()
     def step(self, grad_scale: float = 1.0, lr: Optional[float] = None) -> None:
         self.begin_step()
+        if self._clip is not None:
+            self._clip_scalar(grad_scale)
         for si, s in enumerate(self.spaces):
             self.update(si, 0, s.numel, grad_scale, lr)
+
+
+class FusedLAMB(_AdamMoments):
+    """LAMB (You et al., 2020): Adam's moments, and per tensor ``t`` of a space
+
+        u = (m / bc1) / (sqrt(v / bc2) + eps) + wd * w
+        w -= lr * r_t * u,   r_t = |w_t| / |u_t|  (1 when either norm is 0)
+
+    with the trust ratio ``r_t`` on the spaces named in ``adapt_groups`` (default:
+    the decay groups, i.e. ``"weights"``) and 1 elsewhere.  Two passes over a
+    space and no per-element state beyond ``m`` and ``v``: stage 1 updates the
+    moments and leaves per-chunk partial sums of ``w^2`` and ``u^2``, one small
+    launch turns them into the ratios, stage 2 recomputes ``u`` and applies it.
+    Every sum runs in a fixed order, so a step is bit-repeatable.  The step is
+    not elementwise: there is no ranged ``update``, and every space needs its
+    tensors' ``segments`` (the compact parameter-server shards have none)."""
+
+    def __init__(self, spaces, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, decay_groups=None,
+                 adapt_groups=None, max_grad_norm=None):
+        for s in _as_spaces(spaces):
+            if s.segments is None:
+                raise ValueError(f"FusedLAMB: optimizer space {s.name!r} has no per-tensor segments "
+                                 "(a sharded layout); LAMB needs whole tensors for its trust ratios")
+        super().__init__(spaces, lr, betas, eps, weight_decay, decay_groups, max_grad_norm)
+        self.adapt_groups = set(adapt_groups) if adapt_groups is not None else set(self.decay_groups)
+        self._part, self._ratio = [], []
+        for s, t in zip(self.spaces, self._tables() if self._t is not None else []):
+            adapt = self._adapts(s)
+            self._part.append(torch.zeros(2 * t.nchunks, dtype=torch.float32, device=s.device) if adapt else None)
+            self._ratio.append(torch.ones(t.ntens, dtype=torch.float32, device=s.device) if adapt else None)
+
+    def _adapts(self, s: OptSpace) -> bool:
+        return s.name in self.adapt_groups or not s.name
+
+    @torch.no_grad()
+    def step(self, grad_scale: float = 1.0, lr: Optional[float] = None) -> None:
+        self.begin_step()
+        lr = self.lr if lr is None else lr
+        if self._clip is not None:
+            self._clip_scalar(grad_scale)
+        for si, s in enumerate(self.spaces):
+            if self._cpu(s):
+                self._cpu_step(si, grad_scale, lr)
+                continue
+            t, g = self._tables()[si], s.grad
+            part, ratio, wd = self._part[si], self._ratio[si], self._wd(s)
+            _lib.call("kfa_lamb_stage1", _lib.ptr(s.w), _lib.ptr(g), int(g.dtype == torch.bfloat16),
+                      _lib.ptr(self.m[si]), _lib.ptr(self.v[si]), _lib.ptr(t.chunks), t.nchunks, _lib.ptr(part),
+                      self.b1, self.b2, self.eps, wd, grad_scale, _lib.ptr(self._bc), self._dcoef(), _lib.stream())
+            if ratio is not None:
+                _lib.call("kfa_lamb_ratio", _lib.ptr(part), _lib.ptr(t.tens), t.ntens, _lib.ptr(ratio),
+                          _lib.stream())
+            _lib.call("kfa_lamb_stage2", _lib.ptr(s.w), _lib.ptr(s.wb), _lib.ptr(self.m[si]), _lib.ptr(self.v[si]),
+                      _lib.ptr(t.chunks), t.nchunks, _lib.ptr(ratio), lr, self.eps, wd, _lib.ptr(self._bc),
+                      _lib.stream())
+
+    def _cpu_step(self, si: int, grad_scale: float, lr: float) -> None:
+        s = self.spaces[si]
+        bc1 = 1.0 - self.b1 ** self.step_count
+        bc2 = 1.0 - self.b2 ** self.step_count
+        wd, adapt = self._wd(s), self._adapts(s)
+        gr = s.grad
+        for a, n in s.segments:
+            w, m, v = s.w[a:a + n], self.m[si][a:a + n], self.v[si][a:a + n]
+            d = gr[a:a + n].float() * grad_scale
+            if self._clip is not None:
+                d = d * self._clip[1]
+            m.mul_(self.b1).add_(d, alpha=1 - self.b1)
+            v.mul_(self.b2).addcmul_(d, d, value=1 - self.b2)
+            u = (m / bc1) / ((v / bc2).sqrt() + self.eps) + wd * w
+            r = 1.0
+            if adapt:
+                wn, un = float(w.norm()), float(u.norm())
+                if wn > 0 and un > 0:
+                    r = wn / un
+            w.add_(u, alpha=-lr * r)
+        if s.wb is not None:
+            s.wb.copy_(s.w)

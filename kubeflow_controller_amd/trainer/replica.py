@@ -208,6 +208,23 @@ def _async_mode(spec: ClusterSpec, args) -> bool:
     return args.ps_mode == "async"
 
 
+def _check_whole_gradient(spec: ClusterSpec, args, async_mode: bool) -> None:
+    """LAMB's per-tensor norms and the clip's global norm need every worker to hold the
+    whole reduced gradient: the all-reduce layout (or one replica).  Raises ValueError for
+    the async PS mode, whose PS tasks keep Adam / SGD, and for the sharded collective layouts."""
+    if args.optimizer != "lamb" and args.max_grad_norm is None:
+        return
+    if args.optimizer == "sgd":
+        raise ValueError("--max_grad_norm: gradient clipping is not built for --optimizer sgd (use adam or lamb)")
+    if async_mode:
+        raise ValueError("--optimizer lamb / --max_grad_norm are not available in the async parameter-server "
+                         "mode: its PS tasks apply Adam or SGD per pushed gradient (parallel/async_ps.py); "
+                         "run the job without PS tasks (all-reduce)")
+    if spec.ps and spec.num_workers > 1 and not spec.is_local:
+        raise ValueError("--optimizer lamb / --max_grad_norm need the whole gradient on every worker: with PS tasks "
+                         "the collective mode shards it over the owners; run the job without PS tasks (all-reduce)")
+
+
 # ------------------------------------------------------------------ roles
 TRANSPORT_KEY = "kfa/async_ps/transport"
 
@@ -427,7 +444,8 @@ def run_worker(spec: ClusterSpec, args) -> int:
                     weight_decay=args.weight_decay, compute_dtype=torch.bfloat16 if (use_gpu and args.bf16) else None,
                     bucket_mb=args.bucket_mb, dist_info=DistInfo(rank, world, 0, device),
                     channels_last=model.__class__.__name__ == "ResNet", ps=num_ps, ps_placement=args.ps_placement,
-                    grad_reduce_dtype=None if args.grad_reduce == "bf16" else torch.float32)
+                    grad_reduce_dtype=None if args.grad_reduce == "bf16" else torch.float32,
+                    max_grad_norm=args.max_grad_norm)
     model = engine.model
     resumed = engine.restore(args.model_dir) if args.model_dir else 0
     if resumed:
@@ -559,7 +577,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--train_steps", type=int, default=200)
     ap.add_argument("--batch_size", type=int, default=100)
     ap.add_argument("--learning_rate", type=float, default=0.01)
-    ap.add_argument("--optimizer", default="adam", choices=["adam", "sgd"])
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "sgd", "lamb"],
+                    help="lamb: Adam moments with per-tensor trust ratios (the large-batch BERT recipe); "
+                         "collective / local modes only")
+    ap.add_argument("--max_grad_norm", type=float, default=None,
+                    help="clip the gradient to this global L2 norm before the update (adam, lamb; "
+                         "collective / local modes only)")
     ap.add_argument("--momentum", type=float, default=0.0)
     ap.add_argument("--weight_decay", type=float, default=0.0)
     ap.add_argument("--hidden_units", type=int, default=100)
@@ -624,8 +647,10 @@ def main(argv: Optional[list] = None) -> int:
     spec = parse_cluster(args)
     if not spec.is_local:
         _aggregate(spec, args)  # validates --replicas_to_aggregate before any connection is made
+    async_mode = _async_mode(spec, args)
+    _check_whole_gradient(spec, args, async_mode)  # before any connection is made
     _install_stack_dumps()
-    if _async_mode(spec, args):
+    if async_mode:
         if spec.is_ps:  # a PS serves for as long as the workers train: no step-level guard
             return run_ps_async(spec, args)
         _arm_watchdog(args)

@@ -34,6 +34,9 @@ def main(argv=None) -> int:
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--ps", type=int, default=0, help="parameter-server shard owners (0 = all-reduce)")
     ap.add_argument("--bucket-mb", type=float, default=32.0)
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "lamb"])
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip the gradient to this global L2 norm (all-reduce layout only)")
     args = ap.parse_args(argv)
     info = init_distributed()
     if info.device.type != "cuda":
@@ -56,8 +59,8 @@ def main(argv=None) -> int:
         batch = prepare_batch(model, *synthetic_batch(cfg, args.batch, g, "cpu"), info.device)
         loss_fn, unit, flops = wide_deep_loss, "examples/sec", None
         metric = f"{args.model} training examples/sec (whole node)"
-    engine = Engine(model, loss_fn, optimizer="adam", lr=args.lr, weight_decay=0.01, bucket_mb=args.bucket_mb,
-                    dist_info=info, channels_last=False, ps=args.ps)
+    engine = Engine(model, loss_fn, optimizer=args.optimizer, lr=args.lr, weight_decay=0.01, bucket_mb=args.bucket_mb,
+                    dist_info=info, channels_last=False, ps=args.ps, max_grad_norm=args.max_grad_norm)
     from kubeflow_controller_amd.ops import routes as _routes
     r = timed_steps(engine, batch, args.steps, args.warmup)
     ms = r["elapsed"] / args.steps * 1e3
@@ -69,6 +72,7 @@ def main(argv=None) -> int:
                "config": {"model": args.model, "global_batch": args.batch * info.world,
                           "seq_len": args.seq if args.model.startswith("bert") else None,
                           "parallelism": (f"{info.world}w+{args.ps}ps" if args.ps else f"dp{info.world}"),
+                          "optimizer": args.optimizer, "max_grad_norm": args.max_grad_norm,
                           "routes": _routes.summary(), "loss": r["loss"]}}
         if flops:
             out["tflops_per_gpu"] = round(flops / (ms / 1e3) / 1e12, 1)
