@@ -33,16 +33,36 @@
 // its two 256-co halves (64 KB each) pass through the slot once per tile from L2 by
 // LDS-DMA, the first under the wgrad's MFMAs, the second exposed (one slot).
 //
-// LDS: Ci = 64: image 32 + W 32 + y2 8 + coef 3 = 75 KB, two blocks per CU;
-//      Ci = 128: image 64 + W slot 64 + y2 16 + coef 6 = 150 KB, one block (8 waves) per CU.
-// Registers: Ci = 64 keeps the whole next tile's g / x3 / bits loads (72 VGPRs) in flight
-// under the current tile's MFMAs and epilogue.  Ci = 128 holds 128 dW registers per lane: with
-// 256 per lane at two waves per SIMD the next tile's loads are issued after the epilogue
-// (only the y2 DMA, which needs no registers, runs ahead).
-// The epilogue stages each wave's dX2 rows in the image rows that wave itself wrote:
-// no other wave writes there, and every wave's reads of the image are behind a barrier by then.
+// LDS: Ci = 64: image 32 + W 32 + y2 8 + coef 3 + bn2 0.75 = 75.75 KB, two blocks per CU;
+//      Ci = 128: image 64 + W slot 64 + y2 16 + coef 6 + bn2 1.5 = 151.5 KB, one block (8 waves) per CU.
+// (bn2: mean | scale | shift of the BatchNorm whose backward statistics the epilogue gathers.)
+//
+// Epilogue (this file's own; conv_epilogue.h's staging, rounding and statistics): each wave stages
+// its dX2 rows in the image rows that wave itself wrote (no other wave writes there, and every
+// wave's reads of the image are behind a barrier by then) with inline-asm ds_write_b64 /
+// ds_read_b128 under its own lgkmcnt, so hipcc sees no LDS access there and places no vmcnt(0)
+// for the LDS-DMA and the loads in flight.  Its x2 operand (2 x 16 B + 2 bit bytes per lane) is
+// loaded BEFORE the next tile's prefetch: vmcnt retires in order, the wait hipcc counts for it
+// (vmcnt(24) or more) leaves everything younger in flight.
+//
+// Loads in flight, per tile (vm_wait<0> = the kernel's own full wait):
+//   Ci = 64   image formed from gv / xv / bits (hipcc's counted waits) . vm_wait<0> (y2 DMA landed)
+//             . x2 loads . the WHOLE next tile's g / x3 / bits (24 loads, 72 VGPRs; past the block's
+//             last tile the same loads at an offset past the extents, so every trip counts alike)
+//             . barrier . dgrad + wgrad MFMAs . barrier . next y2 DMA . epilogue . back edge:
+//             the prefetch and the DMA stay in flight from their issue to the next image.
+//             226 VGPRs, no scratch.
+//   Ci = 128  128 dW registers per lane of 256 (two waves per SIMD): image . vm_wait<0> . barrier
+//             . W half 0 DMA . wgrad . vm_wait<0> . x2 loads . dgrad half 0 . barrier . W half 1 DMA
+//             . the FIRST HALF of the next tile's loads (12 loads, 36 VGPRs: what is free from here
+//             to the end of the epilogue) . vm_wait<12> (the DMA, not the loads) . dgrad half 1
+//             . barrier . next y2 DMA . epilogue . the second half of the loads (nothing over it).
+//             The load plans are re-formed per use from the lane id (held across the tile they
+//             went to scratch, and a scratch reload is a vmcnt(0)).  256 VGPRs, 13 spilled dwords
+//             (two dW fragments parked across the dgrad and the epilogue, one dword outside the loop).
 // Rows past K: g / x3 / y2 read 0 through the buffer range check (the dx3 rows are then
-// k[c], multiplied by y2 = 0 in dW; their dX2 rows are dropped by the epilogue's range check).
+// k[c], multiplied by y2 = 0 in dW; their dX2 rows are dropped by the epilogue's range check
+// and masked out of the statistics).
 #include "common.h"
 #include "tile.h"
 #include "conv_epilogue.h"
@@ -66,6 +86,15 @@ __device__ __forceinline__ short8 lds_rd16(unsigned la) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(la), "i"(OFF) : "memory");
   return v;
 }
+// ds_write_b64 at la (inline asm: the epilogue's staging stays out of hipcc's sight, which would
+// otherwise drain vmcnt(0) -- the next tile's loads and y2 DMA -- before any LDS access it can see)
+typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void lds_wr8(unsigned la, uintx2 v) {
+  asm volatile("ds_write_b64 %0, %1" ::"v"(la), "v"(v) : "memory");
+}
+__device__ __forceinline__ void unpack8f(const short8 v, float f[8]) {
+  unpack8(__builtin_bit_cast(uint4, v), f);
+}
 
 template <int CI>
 __global__ __launch_bounds__(4 * CI, CI == 64 ? 2 : 1) void conv3_bwd_fused_kernel(
@@ -88,6 +117,7 @@ __global__ __launch_bounds__(4 * CI, CI == 64 ? 2 : 1) void conv3_bwd_fused_kern
   __shared__ __attribute__((aligned(16))) bf16_t s_w[CI * 256];
   __shared__ __attribute__((aligned(16))) bf16_t s_y[TP * CI];
   __shared__ __attribute__((aligned(16))) float s_coef[3 * CO];
+  __shared__ __attribute__((aligned(16))) float s_bn[3 * CI];  // bn2: mean | scale | shift (0 where not given)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wp = wave & 3, wc = wave >> 2;  // dgrad wave tile: pixels 16 wp .., ci 64 wc ..
@@ -101,8 +131,12 @@ __global__ __launch_bounds__(4 * CI, CI == 64 ? 2 : 1) void conv3_bwd_fused_kern
   const __amdgpu_buffer_rsrc_t rG = rsrc(G, big_bytes), rX = rsrc(X3, big_bytes);
   const __amdgpu_buffer_rsrc_t rM = rsrc(MB, big_bytes >> 4);
   const __amdgpu_buffer_rsrc_t rY = rsrc(Y2, g.d_bytes), rD = rsrc(DX2, g.d_bytes);
-  const __amdgpu_buffer_rsrc_t rBX = rsrc(bnb.x ? bnb.x : DX2, bnb.x ? g.d_bytes : 0u);
-  const EpiRes er{rD, rsrc(DX2, 0u), rBX, rsrc(DX2, 0u)};
+  // bn2's backward statistics (the epilogue below): its input x2 and, where the ReLU mask is kept as
+  // bits, the bit bytes (one per 16-B chunk); zero extents read 0 without a branch
+  const bool bstat = stats && bnb.x;
+  const bool bmask = bstat && bnb.relu && bnb.mb, xmask = bstat && bnb.relu && !bnb.mb;
+  const __amdgpu_buffer_rsrc_t rBX = rsrc(bstat ? (const void*)bnb.x : DX2, bstat ? g.d_bytes : 0u);
+  const __amdgpu_buffer_rsrc_t rBM = rsrc(bmask ? (const void*)bnb.mb : DX2, bmask ? g.d_bytes >> 4 : 0u);
 
   // weight half h into the slot: row ci, 16-B chunk c (of the half's 32) stored at c ^ (ci & 15)
   // (the 16 rows of a fragment read then hit 16 distinct chunks of one 256-B bank cycle)
@@ -128,6 +162,10 @@ __global__ __launch_bounds__(4 * CI, CI == 64 ? 2 : 1) void conv3_bwd_fused_kern
     }
   }
   for (int i = tid; i < 3 * CO; i += NT) s_coef[i] = coef[i];
+  if (tid < 3 * CI) {
+    const int a = tid / CI, n = tid % CI;
+    s_bn[tid] = !bstat ? 0.f : a == 0 ? bnb.mean[n] : xmask ? bnb.ss[(a - 1) * CI + n] : 0.f;
+  }
   __syncthreads();
   // prologue plan: load i of a lane is row RPW*wave + RSTEP*i + lane / CPR, chunk lane % CPR (fixed
   // per lane: its 8 channels' coefficients are re-read from LDS per tile, not held in registers)
@@ -145,21 +183,58 @@ __global__ __launch_bounds__(4 * CI, CI == 64 ? 2 : 1) void conv3_bwd_fused_kern
 
   uint4 gv[LR], xv[LR];
   unsigned bits[LR];
-  auto issue_regs = [&](int t) __attribute__((always_inline)) {
-    const unsigned so = (unsigned)t * (unsigned)(TP * CO * 2);
+  // (live: false past the block's last tile -- every offset then lies past the extents, the loads
+  // return 0 without traffic, and the loop body issues the same number of loads on every trip,
+  // so the waits hipcc counts for them never fall back to vmcnt(0))
+  auto issue_regs = [&](int t, bool live, auto i0c, auto i1c) __attribute__((always_inline)) {
+    constexpr int I0 = decltype(i0c)::value, I1 = decltype(i1c)::value;  // loads [I0, I1) of the tile
+    const unsigned so = live ? (unsigned)t * (unsigned)(TP * CO * 2) : kOOB;
+    unsigned pv = pvo;
+    if constexpr (!PREFETCH) {  // (Ci = 128: the plan formed per use from the lane id; held across the tile it went to scratch)
+      int lp = lane;
+      asm volatile("" : "+v"(lp));
+      pv = (unsigned)((RPW * wave + lp / CPR) * CO + (lp % CPR) * 8) * 2u;
+    }
 #pragma unroll
-    for (int i = 0; i < LR; i++) {
-      const unsigned vo = pvo + (unsigned)(i * RSTEP * CO * 2);
+    for (int i = I0; i < I1; i++) {
+      const unsigned vo = pv + (unsigned)(i * RSTEP * CO * 2);
       gv[i] = bload16<2>(rG, vo + so);
       bits[i] = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rM, (vo + so) >> 4, 0, 0);
     }
 #pragma unroll
-    for (int i = 0; i < LR; i++) xv[i] = bload16<2>(rX, pvo + (unsigned)(i * RSTEP * CO * 2) + so);
+    for (int i = I0; i < I1; i++) xv[i] = bload16<2>(rX, pv + (unsigned)(i * RSTEP * CO * 2) + so);
   };
+  constexpr std::integral_constant<int, 0> kL0{};
+  constexpr std::integral_constant<int, CI == 64 ? LR : LR / 2> kLE{};  // loads issued early (Ci = 128: half the tile)
+  constexpr std::integral_constant<int, LR> kLR{};
   auto issue_y = [&](int t) __attribute__((always_inline)) {
+    int ly = lane;
+    if constexpr (!PREFETCH) asm volatile("" : "+v"(ly));  // (as above)
 #pragma unroll
-    for (int i = 0; i < YI; i++)
-      buf_dma16(rY, s_y + (wave * YI + i) * YRPI * CI, y_vo[i], t * (TP * CI * 2));
+    for (int i = 0; i < YI; i++) {
+      const int row = (wave * YI + i) * YRPI + ly / YCPR;
+      const int vo = PREFETCH ? y_vo[i] : (row * CI + (((ly % YCPR) ^ img_swz<CI>(row)) << 3)) * 2;
+      buf_dma16(rY, s_y + (wave * YI + i) * YRPI * CI, vo, t * (TP * CI * 2));
+    }
+  };
+  // epilogue plan of a wave tile (16 pixels x 64 ci): 16-B piece i of a lane is row 8 i + lane / 8,
+  // chunk lane % 8.  Its x2 operand (and bit byte) is loaded at the top of the tile, BEFORE the next
+  // tile's prefetch: vmcnt retires in order, so the epilogue's wait for it leaves the prefetch in flight
+  uint4 bxv[2];
+  unsigned bmv[2];
+  auto epi_off = [&](int t, int i, int le) __attribute__((always_inline)) {
+    const int m = t * TP + wp * 16 + i * 8 + (le >> 3);
+    return m < g.M ? (unsigned)(m * CI + wc * 64 + (le & 7) * 8) * 2u : kOOB;
+  };
+  auto issue_bx = [&](int t) __attribute__((always_inline)) {
+    int le = lane;
+    asm volatile("" : "+v"(le));
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+      const unsigned off = epi_off(t, i, le);
+      bxv[i] = bload16<KFA_CONV_EPI_LOAD_AUX>(rBX, off);
+      bmv[i] = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rBM, off >> 4, 0, 0);
+    }
   };
 
   floatx4 accw[TNW][4], accd[4][1];
@@ -233,8 +308,86 @@ __global__ __launch_bounds__(4 * CI, CI == 64 ? 2 : 1) void conv3_bwd_fused_kern
     });
   };
 
+  // dX2 wave tile out: conv_epilogue<1, 4, 1, kEpiStats | kEpiBnBwd>'s staging, rounding, stores and
+  // statistics (conv_epilogue.h), with the LDS traffic as inline asm under the kernel's own lgkmcnt
+  // and bn2's per-channel operands from s_bn.  MFMA leaves lane (fr, fq) 4 consecutive ci of pixel fr
+  // per ni; staged as [16 pixel][64 ci] rows of 128 B (chunk ^ (row & 7)) in the wave's own image
+  // rows, every lane then stores two 16-B pieces.  No vector-memory wait but the one hipcc counts
+  // for bxv / bmv.
+  auto epilogue = [&](int t) __attribute__((always_inline)) {
+    int le = lane;
+    asm volatile("" : "+v"(le));
+    const int fr = le & 15, fq = le >> 4, c = le & 7, r0 = le >> 3;
+    const unsigned st = lds_addr(s_img) + (unsigned)(RPW * wave * 256);
+    const unsigned wa = st + (unsigned)(fr * 128 + (fq & 1) * 8), wx = (unsigned)((fq >> 1) ^ (fr & 7));
+    lds_wr8(wa + ((0u ^ wx) << 4), uintx2{pack2(accd[0][0][0], accd[0][0][1]), pack2(accd[0][0][2], accd[0][0][3])});
+    lds_wr8(wa + ((2u ^ wx) << 4), uintx2{pack2(accd[1][0][0], accd[1][0][1]), pack2(accd[1][0][2], accd[1][0][3])});
+    lds_wr8(wa + ((4u ^ wx) << 4), uintx2{pack2(accd[2][0][0], accd[2][0][1]), pack2(accd[2][0][2], accd[2][0][3])});
+    lds_wr8(wa + ((6u ^ wx) << 4), uintx2{pack2(accd[3][0][0], accd[3][0][1]), pack2(accd[3][0][2], accd[3][0][3])});
+    const unsigned ra = st + (unsigned)(r0 * 128 + ((c ^ r0) << 4));
+    short8 ov[2];
+    ov[0] = lds_rd16<0>(ra);  // (LDS serves one wave's requests in order: the reads see the writes)
+    ov[1] = lds_rd16<1024>(ra);
+    if (!bstat) {  // wave-uniform
+      lgkm_wait<0>();
+      __builtin_amdgcn_sched_barrier(0);
+      bstore16<KFA_CONV_STORE_AUX>(rD, epi_off(t, 0, le), __builtin_bit_cast(uint4, ov[0]));
+      bstore16<KFA_CONV_STORE_AUX>(rD, epi_off(t, 1, le), __builtin_bit_cast(uint4, ov[1]));
+    } else {
+      const unsigned ba = lds_addr(s_bn) + (unsigned)((wc * 64 + c * 8) * 4);
+      const short8 m0 = lds_rd16<0>(ba), m1 = lds_rd16<16>(ba);
+      const short8 a0 = lds_rd16<CI * 4>(ba), a1 = lds_rd16<CI * 4 + 16>(ba);
+      const short8 b0 = lds_rd16<CI * 8>(ba), b1 = lds_rd16<CI * 8 + 16>(ba);
+      lgkm_wait<0>();
+      __builtin_amdgcn_sched_barrier(0);
+      const floatx4 mu[2] = {__builtin_bit_cast(floatx4, m0), __builtin_bit_cast(floatx4, m1)};
+      const floatx4 sc[2] = {__builtin_bit_cast(floatx4, a0), __builtin_bit_cast(floatx4, a1)};
+      const floatx4 sf[2] = {__builtin_bit_cast(floatx4, b0), __builtin_bit_cast(floatx4, b1)};
+      float s1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        const unsigned off = epi_off(t, i, le);
+        bstore16<KFA_CONV_STORE_AUX>(rD, off, __builtin_bit_cast(uint4, ov[i]));
+        float f[8], xf[8];
+        unpack8f(ov[i], f);  // the bf16-rounded values the BatchNorm will see
+        unpack8(bxv[i], xf);
+        // ReLU mask: the bit byte, or y > 0 recomputed as bn_apply evaluated it, or none (the form is
+        // wave-uniform: selected with mask arithmetic, not branches); rows past K take no part
+        const unsigned mbits = off == kOOB ? 0u : bmask ? bmv[i] : 0xffu;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          const bool pos = fmaf(xf[j], sc[j >> 2][j & 3], sf[j >> 2][j & 3]) > 0.f;
+          const bool keep = (((mbits >> j) & 1u) != 0u) & (pos | !xmask);
+          const float dz = keep ? f[j] : 0.f;
+          s1[j] += dz;
+          s2[j] += dz * (xf[j] - mu[j >> 2][j & 3]);
+        }
+      }
+      // lanes sharing chunk c (xor 8, 16, 32) reduced by butterfly; lane L then publishes channel
+      // (L % 8) * 8 + L / 8: one 64-lane atomic per statistic covers the wave's 64 channels
+#pragma unroll
+      for (int o = 8; o < 64; o <<= 1)
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          s1[j] += __shfl_xor(s1[j], o, 64);
+          s2[j] += __shfl_xor(s2[j], o, 64);
+        }
+      float a = s1[0], b = s2[0];
+#pragma unroll
+      for (int j = 1; j < 8; j++) {
+        a = r0 == j ? s1[j] : a;
+        b = r0 == j ? s2[j] : b;
+      }
+      float* slot = stats + (long)(blockIdx.x % kBnSlots) * 2 * CI + (wc * 64 + c * 8 + r0);
+      __hip_atomic_fetch_add(slot, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(slot + CI, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) accd[i][0] = floatx4{0.f, 0.f, 0.f, 0.f};
+  };
+
   issue_y(t0);
-  issue_regs(t0);
+  issue_regs(t0, true, kL0, kLR);
   for (int it = 0; it < nt; it++) {
     const int t = t0 + it;
     // dx3 tile -> LDS image (bn_bwd_apply's expression and rounding)
@@ -263,9 +416,11 @@ __global__ __launch_bounds__(4 * CI, CI == 64 ? 2 : 1) void conv3_bwd_fused_kern
           pack8(o);
     }
     vm_wait<0>();  // this tile's y2 DMA landed (the youngest load in flight; the last tile's stores drain too)
-    if constexpr (PREFETCH)
-      if (it + 1 < nt) issue_regs(t + 1);  // the whole next tile in flight under this tile's MFMAs and epilogue
-    lds_barrier();                         // image and y2 tile published (also the resident weight)
+    if constexpr (PREFETCH) {
+      issue_bx(t);                        // the epilogue's x2 operand: older than the prefetch, so waiting for it leaves the prefetch alone
+      issue_regs(t + 1, it + 1 < nt, kL0, kLR);  // the whole next tile in flight under this tile's MFMAs and epilogue
+    }
+    lds_barrier();                                           // image and y2 tile published (also the resident weight)
 
     if constexpr (WH == 1) {
       dgrad_half(std::integral_constant<int, 0>{});
@@ -278,26 +433,23 @@ __global__ __launch_bounds__(4 * CI, CI == 64 ? 2 : 1) void conv3_bwd_fused_kern
       lds_barrier();
 #pragma unroll
       for (int i = 0; i < 4; i++) accd[i][0] = floatx4{0.f, 0.f, 0.f, 0.f};  // (not live across the wgrad)
+      issue_bx(t);  // (not held across the wgrad, where the registers run out; lands under the dgrad and the second half's DMA)
       dgrad_half(std::integral_constant<int, 0>{});
       lds_barrier();  // every wave is done reading half 0
       w_dma(1);       // (one slot: this half's L2 latency is exposed)
-      vm_wait<0>();
+      // the first half of the next tile's loads (36 registers: what is free beside dW from here to the
+      // end of the epilogue), younger than the DMA so that its wait leaves them in flight
+      issue_regs(t + 1, it + 1 < nt, kL0, kLE);
+      vm_wait<3 * (LR / 2)>();
       lds_barrier();
       dgrad_half(std::integral_constant<int, 1>{});
     }
     lds_barrier();  // every wave is done reading the image, the y2 tile and the weight slot
     if (it + 1 < nt) issue_y(t + 1);
     // dX2 tile out (LDS-staged 16-B stores, bn2's backward statistics), staged in this wave's own image rows
-    // (the statistics' per-channel operands and the epilogue's lane-derived offsets are
-    // re-formed per tile: hoisted out of the tile loop they were held in scratch)
-    BnBwd bt = bnb;
-    int le = lane;
-    asm volatile("" : "+s"(bt.mean), "+s"(bt.ss), "+v"(le));
-    conv_epilogue<1, 4, 1, kEpiStats | kEpiBnBwd>(g, accd, reinterpret_cast<char*>(s_img + RPW * wave * 128), false,
-                                                  le, t * TP + wp * 16, wc * 64, 1, 1.f, 1.f, true, nullptr, stats, bt,
-                                                  er);
+    epilogue(t);
     if constexpr (!PREFETCH)
-      if (it + 1 < nt) issue_regs(t + 1);
+      if (it + 1 < nt) issue_regs(t + 1, true, kLE, kLR);  // the second half: nothing over it
   }
 
   // this block's complete dW partial (slab b)
