@@ -62,7 +62,9 @@ class Bottleneck(nn.Module):
         st = self.training
         if self.downsample is None:
             y = self.bn1(self.conv1(x, join=join, bn_stats=st), bwd_link=st)
-            y = self.bn2(self.conv2(y, bn_stats=st), bwd_link=st, lazy=st and LAZY_BN2)
+            # (conv2's output feeds bn2 alone: the same hand-off, ops.conv.Conv2BwdLink, where conv2 is the
+            # 64-channel stride-1 3x3 the one-pass kernel covers)
+            y = self.bn2(self.conv2(y, bn_stats=st, tail_link=st), bwd_link=st, lazy=st and LAZY_BN2)
             # conv3's output feeds bn3 alone: bn3's backward may leave its input gradient to conv3's
             # one-pass backward (ops.conv.Conv3BwdLink; identity blocks only)
             return self.bn3(self.conv3(y, bn_stats=st, tail_link=st), residual=join.branch(x), bwd_link=st,
@@ -74,7 +76,7 @@ class Bottleneck(nn.Module):
         r = self.downsample["conv"](x, join=join, bn_stats=(DS_SLOTS if dual else st))
         idn = None if dual else self.downsample["bn"](r)
         y = self.bn1(self.conv1(join.branch(x), bn_stats=st), bwd_link=st)
-        y = self.bn2(self.conv2(y, bn_stats=st), bwd_link=st, lazy=st and LAZY_BN2)
+        y = self.bn2(self.conv2(y, bn_stats=st, tail_link=st), bwd_link=st, lazy=st and LAZY_BN2)
         if dual:
             return bn_act_dual(self.bn3, self.conv3(y, bn_stats=st), self.downsample["bn"], r, bwd_link=st)
         return self.bn3(self.conv3(y, bn_stats=st), residual=idn, bwd_link=st)

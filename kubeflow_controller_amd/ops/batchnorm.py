@@ -171,7 +171,7 @@ class _BNActFn(torch.autograd.Function):
         ctx.params = (weight, bias)
         # x = the output of a conv that armed a Conv3BwdLink: this backward may leave dx to it
         # (training, ReLU with residual bits; the dual / downsample form never gets here)
-        ctx.tail = tail if (tail is not None and training and relu and mb is not None and tail.take()) else None
+        ctx.tail = tail if (tail is not None and training and relu and tail.mask_ok(ss, mb) and tail.take()) else None
         return y
 
     @staticmethod
@@ -210,7 +210,7 @@ class _BNActFn(torch.autograd.Function):
                       _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(slots),
                       _lib.ptr(tcoef), M, C, int(ctx.relu), int(direct), _lib.ptr(ss), _lib.ptr(mb), int(pre),
                       _lib.stream())
-            tail.defer(dy, x, mb, tcoef, dx, bool(ctx.relu))
+            tail.defer(dy, x, mb, tcoef, dx, bool(ctx.relu), ss)
         else:
             _lib.call("kfa_bn_bwd_prestats" if pre else "kfa_bn_bwd", _lib.ptr(dy), _lib.ptr(x), _lib.ptr(y),
                       _lib.ptr(weight), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(dx), _lib.ptr(dres),
@@ -238,7 +238,8 @@ def bn_act(x, weight, bias, running_mean, running_var, residual=None, training=T
         prestats = False
     link = BnBwdLink() if (bwd_link and training) else None
     lz = LazyBN() if (lazy and training and relu and residual is None and MASK_FROM_X and x.is_cuda) else None
-    tail = getattr(x, "_kfa_conv3_link", None) if (training and residual is not None) else None
+    # the link the producing conv armed: conv3 -> bn3 (+ residual), or conv2 -> bn2 (no residual)
+    tail = getattr(x, "_kfa_conv3_link" if residual is not None else "_kfa_conv2_link", None) if training else None
     y = _BNActFn.apply(x, weight, bias, running_mean, running_var, residual, training, momentum, eps, relu,
                        prestats, link, res_join, lz, tail)
     if link is not None:

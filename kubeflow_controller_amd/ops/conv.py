@@ -131,6 +131,10 @@ _lib.register("kfa_stem_wgrad_fold", [P, P, I, I, I, I, I, I, P])
 _lib.register("kfa_conv3_bwd_fused", [P] * 8 + [I, I, P] + [I] * 9 + [P, P, P, I, P, P, I, P])
 _lib.register("kfa_conv3_bwd_part_floats", [I] * 6, _lib.L)
 _lib.register("kfa_bn_bwd_apply_only", [P] * 5 + [_lib.L, I, I, P, P, P])
+# g2 x2 ss2 coef y1 wt dx1 grad | grad_f32 accumulate | part | Nb H W C Co R S stride pad | stats bn_x bn_mean |
+# bn_relu | bn_ss bn_mb | max_blocks | stream
+_lib.register("kfa_conv2_bwd_fused", [P] * 8 + [I, I, P] + [I] * 9 + [P, P, P, I, P, P, I, P])
+_lib.register("kfa_conv2_bwd_part_floats", [I] * 6, _lib.L)
 
 # Runtime switches (tests compare against the vendor path); env KFA_CONV_IGEMM=0 / KFA_WGRAD=0 disable.
 ENABLED = os.environ.get("KFA_CONV_IGEMM", "1") != "0"
@@ -143,6 +147,9 @@ WGRAD_SIDE = os.environ.get("KFA_CONV_WGRAD_SIDE", "0") == "1"
 # One-pass bn3 backward + conv3 dgrad / wgrad for identity bottleneck tails (csrc/kernels/conv3_bwd.hip,
 # ``Conv3BwdLink``); KFA_CONV3_BWD_FUSED=0 keeps apply + dgrad + wgrad + reduce.  Tests flip the attribute.
 CONV3_BWD_FUSED = os.environ.get("KFA_CONV3_BWD_FUSED", "1") != "0"
+# One-pass bn2 backward + conv2 dgrad / wgrad for the 64-channel stride-1 3x3s (csrc/kernels/conv2_bwd.hip,
+# ``Conv2BwdLink``); KFA_CONV2_BWD_FUSED=0 keeps apply + dgrad + wgrad + reduce everywhere.
+CONV2_BWD_FUSED = os.environ.get("KFA_CONV2_BWD_FUSED", "1") != "0"
 
 
 def igemm_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
@@ -583,12 +590,17 @@ class Conv3BwdLink:
     apply pass, and the separate kernels run as before.  Only a conv whose output feeds that BN
     alone may be armed (the model asks for it: ``conv2d(..., tail_link=True)``)."""
 
-    __slots__ = ("state", "g", "x3", "mb", "coef", "placeholder", "relu")
+    __slots__ = ("state", "g", "x3", "mb", "ss", "coef", "placeholder", "relu")
 
     def __init__(self):
         self.state = "armed"
-        self.g = self.x3 = self.mb = self.coef = self.placeholder = None
+        self.g = self.x3 = self.mb = self.ss = self.coef = self.placeholder = None
         self.relu = True
+
+    @staticmethod
+    def mask_ok(ss, mb) -> bool:
+        """The BatchNorm's ReLU mask source is the one the fused kernel takes: residual bits."""
+        return mb is not None
 
     def take(self) -> bool:
         """bn3's forward: True once, for an armed link."""
@@ -597,11 +609,12 @@ class Conv3BwdLink:
         self.state = "taken"
         return True
 
-    def defer(self, g, x3, mb, coef, placeholder, relu=True) -> None:
+    def defer(self, g, x3, mb, coef, placeholder, relu=True, ss=None) -> None:
         """bn3's backward: dx3 = coef . (g * mb, x3, 1) is left to conv3's backward."""
         if self.state != "taken":
-            raise RuntimeError(f"Conv3BwdLink.defer in state {self.state!r}")
+            raise RuntimeError(f"{type(self).__name__}.defer in state {self.state!r}")
         self.g, self.x3, self.mb, self.coef, self.placeholder, self.relu = g, x3, mb, coef, placeholder, relu
+        self.ss = ss
         self.state = "deferred"
 
     def is_placeholder(self, dy) -> bool:
@@ -615,13 +628,26 @@ class Conv3BwdLink:
             return
         C = self.x3.shape[1] if self.x3.dim() == 4 else self.x3.shape[-1]
         _lib.call("kfa_bn_bwd_apply_only", _lib.ptr(self.g), _lib.ptr(self.x3), None, _lib.ptr(self.coef),
-                  _lib.ptr(self.placeholder), self.x3.numel() // C, C, int(self.relu), None, _lib.ptr(self.mb),
-                  _lib.stream())
+                  _lib.ptr(self.placeholder), self.x3.numel() // C, C, int(self.relu), _lib.ptr(self.ss),
+                  _lib.ptr(self.mb), _lib.stream())
         self.clear()
 
     def clear(self) -> None:
-        self.g = self.x3 = self.mb = self.coef = self.placeholder = None
+        self.g = self.x3 = self.mb = self.ss = self.coef = self.placeholder = None
         self.state = "done"
+
+
+class Conv2BwdLink(Conv3BwdLink):
+    """The same hand-off between a bottleneck's conv2 (3x3 / stride 1, 64 -> 64 channels) and the bn2
+    that consumes its output: bn2's backward runs finalize only and leaves dx2 to
+    ``kfa_conv2_bwd_fused``, which forms its halo image per tile (``x3`` holds bn2's input x2, ``ss``
+    its forward [scale | shift]: the ReLU mask is recomputed from them, there are no mask bits)."""
+
+    __slots__ = ()
+
+    @staticmethod
+    def mask_ok(ss, mb) -> bool:
+        return ss is not None and mb is None
 
 
 def conv3_bwd_shape_ok(x_shape, w_shape, stride: int, pad: int) -> bool:
@@ -717,6 +743,104 @@ def _conv3_bwd_route(x_shape, w_shape, device) -> bool:
         return run
 
     pick = routes.decide("conv3_bwd", key, device, [("sep", lazy(0)), ("fused", lazy(1))])
+    if made is not None:
+        made[1]()
+    return pick == 1
+
+
+def conv2_bwd_shape_ok(x_shape, w_shape, stride: int, pad: int) -> bool:
+    """Shapes ``kfa_conv2_bwd_fused`` covers: 3x3 / stride 1 / pad 1, 64 -> 64 channels, a halo of
+    256 + 2 (W + 1) + 1 rows within the 384-row image, 32-bit offsets."""
+    Nb, Ci, H, W = x_shape
+    Co, _, R, S = w_shape
+    M = Nb * H * W
+    return (R == 3 and S == 3 and stride == 1 and pad == 1 and Ci == 64 and Co == 64 and 0 < M < (1 << 24)
+            and (M + 512) * 128 < (1 << 31) and 256 + 2 * (W + 1) + 1 <= 384)
+
+
+def conv2_bwd_fused(g2, x2, ss2, coef, y1, w, grad, accumulate: bool, bn=None, max_blocks: int = 0,
+                    stride: int = 1, pad: int = 1) -> torch.Tensor:
+    """``kfa_conv2_bwd_fused``: returns dX1; ``grad`` ([Co][3][3][Ci] memory, bf16 / fp32) (+)= dW.
+    ``bn``: the ``BnBwdLink`` of the BatchNorm whose output ``y1`` is (its backward statistics)."""
+    Nb, Ci, H, W = y1.shape
+    Co, _, R, S = w.shape
+    dx = torch.empty((Nb, Ci, H, W), dtype=y1.dtype, device=y1.device, memory_format=torch.channels_last)
+    wt = _transposed_weight(_cl(w), 0, 1, R, 0, 1, S)
+    nfl = _lib.lib().kfa_conv2_bwd_part_floats(Nb, H, W, Ci, Co, max_blocks)
+    part = _lib.workspace(max(nfl, 1) * 4, y1.device, f"conv2_bwd_part{_lib.stream() or 0}").view(torch.float32)
+    bn_ws = None
+    bn_x = bn_mean = bn_ss = bn_mb = None
+    relu = 0
+    if bn is not None:
+        from .batchnorm import bn_slot_workspace
+        bn_ws = bn_slot_workspace(Ci, y1.device)
+        bn_x, bn_mean, bn_ss, bn_mb, relu = bn.x, bn.mean, bn.ss, bn.mb, int(bn.relu)
+    _lib.call("kfa_conv2_bwd_fused", _lib.ptr(g2), _lib.ptr(x2), _lib.ptr(ss2), _lib.ptr(coef), _lib.ptr(y1),
+              _lib.ptr(wt), _lib.ptr(dx), _lib.ptr(grad), int(grad.dtype == torch.float32), int(accumulate),
+              _lib.ptr(part), Nb, H, W, Ci, Co, R, S, stride, pad, _lib.ptr(bn_ws), _lib.ptr(bn_x), _lib.ptr(bn_mean),
+              relu, _lib.ptr(bn_ss), _lib.ptr(bn_mb), max_blocks, _lib.stream())
+    if bn is not None:
+        bn.prestats = True
+    return dx
+
+
+def conv2_bwd_candidates(Nb: int, H: int, W: int, C: int, device) -> tuple:
+    """``([("sep", fn), ("fused", fn)], clean)`` on scratch operands of one shape: bn2's apply pass +
+    conv2's dgrad (with bn1's backward statistics) + wgrad + reduce, against the one-pass kernel;
+    ``clean()`` zeroes the BatchNorm slots the launches filled.  What the ``conv2_bwd`` route times
+    when the shape is not in the table, and ``tools/bench_conv2_bwd.py``."""
+    cl = torch.channels_last
+    bf = dict(dtype=torch.bfloat16, device=device)
+    g2 = torch.randn(Nb, C, H, W, **bf).contiguous(memory_format=cl)
+    x2 = torch.randn(Nb, C, H, W, **bf).contiguous(memory_format=cl)
+    y1 = torch.randn(Nb, C, H, W, **bf).contiguous(memory_format=cl)
+    w = (torch.randn(C, C, 3, 3, **bf) * 0.05).contiguous(memory_format=cl)
+    ss2 = torch.cat([torch.ones(C, device=device), torch.zeros(C, device=device)]).contiguous()
+    coef = torch.randn(3 * C, dtype=torch.float32, device=device) * 0.1
+    dx2 = torch.empty_like(x2)
+    acc = torch.zeros(w.shape, dtype=torch.float32, device=device).contiguous(memory_format=cl)
+    from .batchnorm import BnBwdLink
+    bn = BnBwdLink()
+    bn.x = torch.randn(Nb, C, H, W, **bf).contiguous(memory_format=cl)
+    bn.mean = torch.zeros(C, dtype=torch.float32, device=device)
+    bn.ss = torch.ones(2 * C, dtype=torch.float32, device=device)
+    bn.relu = True
+    M = Nb * H * W
+
+    def clean():  # the timed launches fill the shared slot workspace: leave it zeroed
+        from .batchnorm import bn_slot_workspace
+        bn_slot_workspace(C, device).zero_()
+        bn.prestats = False
+
+    def sep():
+        _lib.call("kfa_bn_bwd_apply_only", _lib.ptr(g2), _lib.ptr(x2), None, _lib.ptr(coef), _lib.ptr(dx2), M, C, 1,
+                  _lib.ptr(ss2), None, _lib.stream())
+        conv_dgrad(dx2, w, y1.shape, 1, 1, None, bn)
+        wgrad_into(y1, dx2, acc, Nb, H, W, C, H, W, C, 3, 3, 1, 1, True)
+
+    def fused():
+        conv2_bwd_fused(g2, x2, ss2, coef, y1, w, acc, True, bn)
+
+    return [("sep", sep), ("fused", fused)], clean
+
+
+def _conv2_bwd_route(x_shape, w_shape, device) -> bool:
+    """The ``conv2_bwd`` decision of one shape: ``fused`` against ``sep`` (the default form; the
+    fused kernel must beat it by the usual margin).  From the committed table, else timed once."""
+    from . import routes
+    Nb, C, H, W = x_shape
+    key = (Nb, H, W, C)
+    made = None  # the scratch operands exist only if the shape has to be timed
+
+    def lazy(i):
+        def run():
+            nonlocal made
+            if made is None:
+                made = conv2_bwd_candidates(Nb, H, W, C, device)
+            made[0][i][1]()
+        return run
+
+    pick = routes.decide("conv2_bwd", key, device, [("sep", lazy(0)), ("fused", lazy(1))])
     if made is not None:
         made[1]()
     return pick == 1
@@ -846,7 +970,8 @@ class _ConvFn(torch.autograd.Function):
             # (dy is unwritten here: the vendor-wgrad tuner is only asked for a decision it already
             # made, never run; the BatchNorm link must carry a mask the fused entry takes)
             bn = ctx.bn_link
-            if (tail.is_placeholder(dy) and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and CONV3_BWD_FUSED
+            on = CONV2_BWD_FUSED if isinstance(tail, Conv2BwdLink) else CONV3_BWD_FUSED
+            if (tail.is_placeholder(dy) and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and on
                     and ctx.join is None and not WGRAD_SIDE and wgrad_ok(x, dy, w)
                     and _own_wgrad_decided(x, w, ctx.stride, ctx.pad)
                     and (bn is None or bn.convs != 1 or bn.y is None)):
@@ -892,8 +1017,12 @@ class _ConvFn(torch.autograd.Function):
         direct = target is not None and target.dtype in (torch.bfloat16, torch.float32) and \
             target.is_contiguous(memory_format=torch.channels_last)
         grad = target if direct else torch.empty_like(w, memory_format=torch.channels_last)
-        dx = conv3_bwd_fused(tail.g, tail.x3, tail.mb, tail.coef, _cl(x), w, grad, direct, bn_link,
-                             stride=ctx.stride, pad=ctx.pad)
+        if isinstance(tail, Conv2BwdLink):  # bn2's apply + conv2's dgrad + wgrad (``conv2_bwd_fused``)
+            dx = conv2_bwd_fused(tail.g, tail.x3, tail.ss, tail.coef, _cl(x), w, grad, direct, bn_link,
+                                 stride=ctx.stride, pad=ctx.pad)
+        else:
+            dx = conv3_bwd_fused(tail.g, tail.x3, tail.mb, tail.coef, _cl(x), w, grad, direct, bn_link,
+                                 stride=ctx.stride, pad=ctx.pad)
         tail.clear()
         if direct:
             notify_grad_ready(wparam)
@@ -983,9 +1112,9 @@ def conv2d(x, w, stride: int = 1, pad: int = 0, join: "GradJoin | None" = None, 
     string names the slot workspace (``ops.batchnorm.bn_slot_workspace`` tag)
     for a BN whose finalize runs later than the next BN's (the downsample BN of
     ``bn_act_dual``); True = the shared one.  ``tail_link``: the caller guarantees the output
-    feeds one training ``BatchNorm2dAct`` (+ residual + ReLU) and nothing else; for a shape the
-    one-pass backward covers and the ``conv3_bwd`` route picks, the output is tagged with an
-    armed ``Conv3BwdLink``."""
+    feeds one training ``BatchNorm2dAct`` (+ residual + ReLU) and nothing else; for a shape a
+    one-pass backward covers and its route (``conv3_bwd`` / ``conv2_bwd``) picks, the output is
+    tagged with an armed ``Conv3BwdLink`` / ``Conv2BwdLink``."""
     tag = bn_stats if isinstance(bn_stats, str) else "bn_slots"
 
     def slots():  # the BN's slot workspace (fetched only on a path whose epilogue fills it)
@@ -998,15 +1127,21 @@ def conv2d(x, w, stride: int = 1, pad: int = 0, join: "GradJoin | None" = None, 
         if stats is not None:
             y._kfa_prestats = True
             y._kfa_prestats_tag = tag
-        if tail is not None:
+        if isinstance(tail, Conv2BwdLink):
+            y._kfa_conv2_link = tail
+        elif tail is not None:
             y._kfa_conv3_link = tail
         return y
 
-    def armed():  # a Conv3BwdLink for this conv's backward, or None
-        if not (tail_link and CONV3_BWD_FUSED and join is None and torch.is_grad_enabled() and x.is_cuda
-                and conv3_bwd_shape_ok(tuple(x.shape), tuple(w.shape), stride, pad)):
+    def armed():  # a Conv3BwdLink / Conv2BwdLink for this conv's backward, or None
+        if not (tail_link and join is None and torch.is_grad_enabled() and x.is_cuda):
             return None
-        return Conv3BwdLink() if _conv3_bwd_route(tuple(x.shape), tuple(w.shape), x.device) else None
+        xs, ws = tuple(x.shape), tuple(w.shape)
+        if CONV3_BWD_FUSED and conv3_bwd_shape_ok(xs, ws, stride, pad):
+            return Conv3BwdLink() if _conv3_bwd_route(xs, ws, x.device) else None
+        if CONV2_BWD_FUSED and conv2_bwd_shape_ok(xs, ws, stride, pad):
+            return Conv2BwdLink() if _conv2_bwd_route(xs, ws, x.device) else None
+        return None
 
     lz = getattr(x, "_kfa_lazy", None)
     if lz is not None and lz.pending and join is None and igemm_ok(x, w):
