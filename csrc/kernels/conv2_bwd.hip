@@ -52,9 +52,6 @@
 #include "tile.h"
 #include "conv_epilogue.h"
 
-int kfa_wgrad_reduce_launch(const float* part, int splits, long total, void* grad, int grad_f32, int accumulate,
-                            hipStream_t s);  // wgrad.hip
-
 namespace {
 using namespace tile;
 
@@ -65,23 +62,6 @@ constexpr int LR2 = HRP2 * 8 / NT2;  // 16-B g2 / x2 loads per lane per tile (6)
 
 __device__ __forceinline__ int halo_swz2(int row) { return ((row >> 1) & 3) << 1; }  // conv_halo_kernel's halo_swz
 
-__device__ __forceinline__ unsigned lds_addr2(const void* p) {
-  return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
-template <int OFF>
-__device__ __forceinline__ short8 lds_rd16(unsigned la) {
-  short8 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(la), "i"(OFF) : "memory");
-  return v;
-}
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void lds_wr16(unsigned la, uint4 v) {
-  const uintx4 w = {v.x, v.y, v.z, v.w};
-  asm volatile("ds_write_b128 %0, %1" ::"v"(la), "v"(w) : "memory");
-}
-__device__ __forceinline__ void lds_wr2(unsigned la, unsigned v) {
-  asm volatile("ds_write_b16 %0, %1" ::"v"(la), "v"(v) : "memory");
-}
 __device__ __forceinline__ short8 and8(const short8 a, const short8 m) {
   const uint4 x = __builtin_bit_cast(uint4, a), y = __builtin_bit_cast(uint4, m);
   return __builtin_bit_cast(short8, make_uint4(x.x & y.x, x.y & y.y, x.z & y.z, x.w & y.w));
@@ -99,8 +79,8 @@ __global__ __launch_bounds__(NT2, 1) void conv2_bwd_fused_kernel(
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntiles = (g.M + TP2 - 1) / TP2, nb = gridDim.x, b = blockIdx.x;
-  const int base = ntiles / nb, rem = ntiles % nb;
-  const int t0 = b * base + (b < rem ? b : rem), nt = base + (b < rem ? 1 : 0);
+  const TileRange own = tile_range(ntiles, nb, b);
+  const int t0 = own.t0, nt = own.nt;
   if (nt == 0) return;
 
   const int HW1 = g.W + 1, HR = TP2 + 2 * HW1;  // staged rows; row HR is the zero row
@@ -122,8 +102,8 @@ __global__ __launch_bounds__(NT2, 1) void conv2_bwd_fused_kernel(
   else if (tid < 320) s_tab[tid] = ss2[tid - 192];
   __syncthreads();
 
-  const unsigned halo_la = lds_addr2(s_halo), w_la = lds_addr2(s_w), mask_la = lds_addr2(s_mask);
-  const unsigned tab_la = lds_addr2(s_tab);
+  const unsigned halo_la = lds_addr(s_halo), w_la = lds_addr(s_w), mask_la = lds_addr(s_mask);
+  const unsigned tab_la = lds_addr(s_tab);
   const int fr = lane & 15, fq = lane >> 4;
 
   uint4 gv[LR2], xv[LR2];
@@ -372,16 +352,15 @@ int conv2_plan(long Nb, int H, int W, int C, int Co, int R, int S, int stride, i
 }
 
 int conv2_blocks(long M, int max_blocks) {
-  const long ntiles = (M + TP2 - 1) / TP2;
-  const long cap = max_blocks > 0 ? max_blocks : kfa_cu_count();
-  return (int)(ntiles < cap ? ntiles : cap);
+  return capped_blocks((M + TP2 - 1) / TP2, max_blocks, 1);
 }
 
 }  // namespace
 
 // floats of the partial workspace kfa_conv2_bwd_fused needs (0: shape not covered); max_blocks > 0 caps the
 // grid (and asks the device nothing)
-KFA_API long kfa_conv2_bwd_part_floats(int Nb, int H, int W, int C, int Co, int max_blocks) {
+// (the pair in kfa_conv3_bwd_part_floats' order, Co then C; both must be 64, so nothing moves for a caller)
+KFA_API long kfa_conv2_bwd_part_floats(int Nb, int H, int W, int Co, int C, int max_blocks) {
   if (conv2_plan(Nb, H, W, C, Co, 3, 3, 1, 1)) return 0;
   return (long)conv2_blocks((long)Nb * H * W, max_blocks) * 9 * 64 * 64;
 }
@@ -403,15 +382,13 @@ KFA_API int kfa_conv2_bwd_fused(const bf16_t* g2, const bf16_t* x2, const float*
   const int rc0 = conv2_plan(Nb, H, W, C, Co, R, S, stride, pad);
   if (rc0) return rc0;
   if (!g2 || !x2 || !ss2 || !coef || !y1 || !wt || !dx1 || !grad || !part) return -1;
-  if (bn_x && bn_relu && !bn_ss && !bn_mb) return -3;
+  if (bn_bwd_mask_missing(bn_x, bn_relu, bn_ss, bn_mb)) return -3;
   const long M = (long)Nb * H * W;
   const unsigned bytes = (unsigned)(M * 128);
   Geo geo{Nb, H, W, 64, H, W, 3, 3, 1, -1, 1, 1, (int)M, 64, 576, H, W, 1, 0, 0, 64, bytes, 9u * 64u * 64u * 2u, bytes};
-  const BnBwd bnb{bn_x, nullptr, bn_ss, bn_mb, bn_mean, bn_relu, nullptr};
+  const BnBwd bnb = bn_bwd_operands(bn_x, bn_mean, bn_relu, bn_ss, bn_mb);
   const int blocks = conv2_blocks(M, max_blocks);
   hipLaunchKernelGGL(conv2_bwd_fused_kernel, dim3(blocks), dim3(NT2), 0, s, g2, x2, coef, ss2, y1, wt, dx1, part,
                      bn_x ? stats : nullptr, bnb, geo);
-  const int rc = kfa_status();
-  if (rc) return rc;
-  return kfa_wgrad_reduce_launch(part, blocks, 9L * 64 * 64, grad, grad_f32, accumulate, s);
+  return reduce_slabs(part, blocks, 9L * 64 * 64, grad, grad_f32, accumulate, s);
 }

@@ -67,31 +67,11 @@
 #include "tile.h"
 #include "conv_epilogue.h"
 
-int kfa_wgrad_reduce_launch(const float* part, int splits, long total, void* grad, int grad_f32, int accumulate,
-                            hipStream_t s);  // wgrad.hip
-
 namespace {
 using namespace tile;
 
 constexpr int TP = 64;  // pixels per tile
 
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
-// ds_read_b128 at la + OFF (inline asm, as conv_igemm_kernel's fragment reads: ordered by the
-// kernel's own lgkmcnt waits; OFF folded into the instruction so a fragment costs no address VGPR)
-template <int OFF>
-__device__ __forceinline__ short8 lds_rd16(unsigned la) {
-  short8 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(la), "i"(OFF) : "memory");
-  return v;
-}
-// ds_write_b64 at la (inline asm: the epilogue's staging stays out of hipcc's sight, which would
-// otherwise drain vmcnt(0) -- the next tile's loads and y2 DMA -- before any LDS access it can see)
-typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void lds_wr8(unsigned la, uintx2 v) {
-  asm volatile("ds_write_b64 %0, %1" ::"v"(la), "v"(v) : "memory");
-}
 __device__ __forceinline__ void unpack8f(const short8 v, float f[8]) {
   unpack8(__builtin_bit_cast(uint4, v), f);
 }
@@ -123,8 +103,8 @@ __global__ __launch_bounds__(4 * CI, CI == 64 ? 2 : 1) void conv3_bwd_fused_kern
   const int wp = wave & 3, wc = wave >> 2;  // dgrad wave tile: pixels 16 wp .., ci 64 wc ..
   // pixel ownership: whole tiles, dealt contiguously (the first `rem` blocks get one more)
   const int ntiles = (g.M + TP - 1) / TP, nb = gridDim.x, b = blockIdx.x;
-  const int base = ntiles / nb, rem = ntiles % nb;
-  const int t0 = b * base + (b < rem ? b : rem), nt = base + (b < rem ? 1 : 0);
+  const TileRange own = tile_range(ntiles, nb, b);
+  const int t0 = own.t0, nt = own.nt;
   if (nt == 0) return;
 
   const unsigned big_bytes = (unsigned)g.M * (unsigned)CO * 2u;
@@ -469,9 +449,7 @@ bool fused_shape_ok(int Ci, int Co, int R, int S, int stride, int pad) {
 
 // blocks with a non-empty pixel range = fp32 partial slabs
 int fused_blocks(long K, int Ci, int max_blocks) {
-  const long ntiles = (K + TP - 1) / TP;
-  const long cap = max_blocks > 0 ? max_blocks : (Ci == 64 ? 2L : 1L) * kfa_cu_count();
-  return (int)(ntiles < cap ? ntiles : cap);
+  return capped_blocks((K + TP - 1) / TP, max_blocks, Ci == 64 ? 2 : 1);
 }
 
 }  // namespace
@@ -497,13 +475,13 @@ KFA_API int kfa_conv3_bwd_fused(const bf16_t* g, const bf16_t* x3, const uint8_t
                                 hipStream_t s) {
   if (!fused_shape_ok(Ci, Co, R, S, stride, pad)) return -1;
   if (!g || !x3 || !mb || !coef || !y2 || !wt || !dx2 || !grad || !part) return -1;
-  if (bn_x && bn_relu && !bn_ss && !bn_mb) return -3;
+  if (bn_bwd_mask_missing(bn_x, bn_relu, bn_ss, bn_mb)) return -3;
   const long K = (long)Nb * P * Q;
   if (K <= 0) return 0;
   if (K >= (1L << 24) || K * Co * 2 >= (long)kOOB) return -2;
   Geo geo{Nb, P, Q, Co, P, Q, 1, 1, 1, 1, 0, 0, (int)K, Ci, Co, P, Q, 1, 0, 0, Ci,
           (unsigned)(K * Co * 2), (unsigned)((long)Ci * Co * 2), (unsigned)(K * Ci * 2)};
-  const BnBwd bnb{bn_x, nullptr, bn_ss, bn_mb, bn_mean, bn_relu, nullptr};
+  const BnBwd bnb = bn_bwd_operands(bn_x, bn_mean, bn_relu, bn_ss, bn_mb);
   const int blocks = fused_blocks(K, Ci, max_blocks);
   float* st = bn_x ? stats : nullptr;
   if (Ci == 64)
@@ -512,7 +490,5 @@ KFA_API int kfa_conv3_bwd_fused(const bf16_t* g, const bf16_t* x3, const uint8_t
   else
     hipLaunchKernelGGL(conv3_bwd_fused_kernel<128>, dim3(blocks), dim3(512), 0, s, g, x3, mb, coef, y2, wt, dx2,
                        part, st, bnb, geo);
-  const int rc = kfa_status();
-  if (rc) return rc;
-  return kfa_wgrad_reduce_launch(part, blocks, (long)Co * Ci, grad, grad_f32, accumulate, s);
+  return reduce_slabs(part, blocks, (long)Co * Ci, grad, grad_f32, accumulate, s);
 }

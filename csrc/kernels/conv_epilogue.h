@@ -1,10 +1,14 @@
 // The output side shared by the implicit-GEMM convolution kernels (conv_igemm.hip)
-// and the fused conv3 backward (conv3_bwd.hip): launch geometry, the fused
-// BatchNorm operands and the LDS-staged epilogue of one wave tile.  Internal
+// and the one-pass conv backward kernels (conv3_bwd.hip, conv2_bwd.hip): launch geometry, the fused
+// BatchNorm operands, the LDS-staged epilogue of one wave tile, and the host side the two one-pass
+// entries share (block cap, BnBwd construction and its refusal, status + slab reduce).  Internal
 // linkage (one copy per translation unit), everything __forceinline__.
 #pragma once
 #include "common.h"
 #include "tile.h"
+
+int kfa_wgrad_reduce_launch(const float* part, int splits, long total, void* grad, int grad_f32, int accumulate,
+                            hipStream_t s);  // wgrad.hip
 
 namespace {
 using namespace tile;
@@ -40,6 +44,29 @@ struct Geo {
   int OH, OW, os, oph, opw, ldd;  // output pixel mapping / row stride (elements)
   unsigned t_bytes, b_bytes, d_bytes;  // buffer extents: out-of-range lanes read 0 / drop stores
 };
+
+// ---- host side of the one-pass backward entries (conv3_bwd.hip, conv2_bwd.hip) ----
+// A BatchNorm with a ReLU whose backward statistics are asked for (x given) needs a mask source the
+// epilogue takes (ss or bits): the entries refuse it with -3 before anything is launched.
+inline bool bn_bwd_mask_missing(const bf16_t* x, int relu, const float* ss, const uint8_t* mb) {
+  return x && relu && !ss && !mb;
+}
+inline BnBwd bn_bwd_operands(const bf16_t* x, const float* mean, int relu, const float* ss, const uint8_t* mb) {
+  return BnBwd{x, nullptr, ss, mb, mean, relu, nullptr};
+}
+// persistent blocks = fp32 partial slabs: one per whole tile, capped at max_blocks, or (max_blocks <= 0)
+// at per_cu blocks per CU -- only that form asks the device
+inline int capped_blocks(long ntiles, int max_blocks, int per_cu) {
+  const long cap = max_blocks > 0 ? max_blocks : (long)per_cu * kfa_cu_count();
+  return (int)(ntiles < cap ? ntiles : cap);
+}
+// after the kernel launch: its status, then the slabs summed into the flat gradient
+inline int reduce_slabs(const float* part, int blocks, long slab_floats, void* grad, int grad_f32, int accumulate,
+                        hipStream_t s) {
+  const int rc = kfa_status();
+  if (rc) return rc;
+  return kfa_wgrad_reduce_launch(part, blocks, slab_floats, grad, grad_f32, accumulate, s);
+}
 
 #ifndef KFA_CONV_EPI_LOAD_AUX
 #define KFA_CONV_EPI_LOAD_AUX 2  // epilogue addend / BN-input loads non-temporal (read once; +0.2 %)

@@ -226,10 +226,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const bf16_
         for (int mi = 0; mi < TM; mi++)
           acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[ks][ni], af[ks][mi], acc[ni][mi], 0, 0, 0);
     };
-    auto rd = [&](const bf16_t* p) {
+    auto rd = [&](const bf16_t* p) {  // (lds_rd16<0> prints an `offset:0`: the same encoding, other text)
       short8 v;
-      const unsigned la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const bf16_t*)p;
-      asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(la) : "memory");
+      asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr(p)) : "memory");
       return v;
     };
     if constexpr (TM + 2 * TN <= 15) {
@@ -304,8 +303,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const bf16_
         // next slice's B DMAs) in front of them
         typedef __attribute__((ext_vector_type(4))) float f32x4;
         f32x4 v[4];
-        const unsigned la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const float*)(ssl + c);
-        const unsigned lb = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const float*)(ssl + g.C + c);
+        const unsigned la = lds_addr(ssl + c), lb = lds_addr(ssl + g.C + c);
         asm volatile("ds_read_b128 %0, %1" : "=v"(v[0]) : "v"(la) : "memory");
         asm volatile("ds_read_b128 %0, %1 offset:16" : "=v"(v[1]) : "v"(la) : "memory");
         asm volatile("ds_read_b128 %0, %1" : "=v"(v[2]) : "v"(lb) : "memory");
@@ -324,13 +322,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const bf16_
 #pragma unroll
         for (int j = 0; j < 8; j++) f[j] = ok ? fmaxf(fmaf(f[j], sc[j], sh[j]), 0.f) : 0.f;
         uint4 o = pack8(f);
-        {  // inline asm: a compiler-visible LDS store got an s_waitcnt vmcnt(0) for the DMAs in flight
-          typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-          const u32x4 w = {o.x, o.y, o.z, o.w};
-          const unsigned la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) bf16_t*)(
-              As + buf * BM * BK + (i * RPP + wave * 8) * BK + lane * 8);
-          asm volatile("ds_write_b128 %0, %1" ::"v"(la), "v"(w) : "memory");
-        }
+        // (inline asm: a compiler-visible LDS store got an s_waitcnt vmcnt(0) for the DMAs in flight)
+        lds_wr16(lds_addr(As + buf * BM * BK + (i * RPP + wave * 8) * BK + lane * 8), o);
         if (pr_y) {
           __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<decltype(__builtin_amdgcn_raw_buffer_load_b128(rY, 0, 0, 0))*>(&o),
                                                  rY, (unsigned)pr_vo[i], (unsigned)pr_soff, 0);
@@ -784,7 +777,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_halo_kernel(const bf16_t
 #pragma unroll
     for (int j = 0; j < TM; j++) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
 
-  const unsigned halo_la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)halo;
+  const unsigned halo_la = lds_addr(halo);
   const unsigned zero_la = halo_la + (unsigned)(((CH - 1) * HRP + HR) * 128 + fq * 16);  // padding row, restaged per tile
   int c_r = 0, c_s = 0, c_h = 0;  // the k-tile compute() runs next: tap (c_r, c_s), sub-image c_h
   // fragment reads ahead of the MFMAs, counted lgkmcnt, as conv_igemm_kernel's 4-wave form
@@ -812,7 +805,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_halo_kernel(const bf16_t
       asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(la) : "memory");
       return v;
     };
-    auto rd = [&](const bf16_t* p) { return rda((unsigned)(uintptr_t)(__attribute__((address_space(3))) const bf16_t*)p); };
+    auto rd = [&](const bf16_t* p) { return rda(lds_addr(p)); };
 #pragma unroll
     for (int i = 0; i < TN; i++) bf[0][i] = rd(Bb + swz128(wn * TN * 16 + i * 16 + fr, fq));
 #pragma unroll

@@ -1,5 +1,5 @@
 // Tile primitives shared by the MFMA matrix kernels (gemm.hip, gemm_ppp.hip,
-// gemm_skinny.hip, conv_igemm.hip, wgrad.hip): one definition of each rule
+// gemm_skinny.hip, conv_igemm.hip, wgrad.hip, conv3_bwd.hip, conv2_bwd.hip): one definition of each rule
 // those kernels are built on.  Everything is __forceinline__ and stateless;
 // the files pull the names in with `using namespace tile;`.
 #pragma once
@@ -95,7 +95,45 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// ---- LDS accesses outside hipcc's sight ----------------------------------------
+// Inline asm, for hand-counted kernels: the access is ordered by the kernel's own
+// lgkmcnt waits and barriers, and hipcc -- which cannot tell an LDS-DMA's
+// destination from any other LDS address -- sees no LDS access in front of which
+// it would drain vmcnt(0), i.e. the loads, stores and DMAs in flight.
+__device__ __forceinline__ unsigned lds_addr(const void* p) {  // the 32-bit LDS address the ds_ instructions take
+  return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
+}
+// ds_read_b128 at la + OFF (OFF folded into the instruction: a fragment costs no address VGPR)
+template <int OFF>
+__device__ __forceinline__ short8 lds_rd16(unsigned la) {
+  short8 v;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(la), "i"(OFF) : "memory");
+  return v;
+}
+typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
+typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void lds_wr16(unsigned la, uint4 v) {
+  const uintx4 w = {v.x, v.y, v.z, v.w};
+  asm volatile("ds_write_b128 %0, %1" ::"v"(la), "v"(w) : "memory");
+}
+__device__ __forceinline__ void lds_wr8(unsigned la, uintx2 v) {
+  asm volatile("ds_write_b64 %0, %1" ::"v"(la), "v"(v) : "memory");
+}
+__device__ __forceinline__ void lds_wr2(unsigned la, unsigned v) {  // the low 16 bits of v
+  asm volatile("ds_write_b16 %0, %1" ::"v"(la), "v"(v) : "memory");
+}
+
 // ---- index helpers -----------------------------------------------------------
+// Persistent blocks over whole tiles: block b of nb owns the contiguous tiles
+// [t0, t0 + nt) of ntiles (the first ntiles % nb blocks get one more).
+struct TileRange {
+  int t0, nt;
+};
+__device__ __forceinline__ TileRange tile_range(int ntiles, int nb, int b) {
+  const int base = ntiles / nb, rem = ntiles % nb;
+  return {b * base + (b < rem ? b : rem), base + (b < rem ? 1 : 0)};
+}
+
 // x / d for 0 <= x < 2^24 via an fp32 reciprocal + one correction step
 // (hipcc's int32 division is a ~40-instruction sequence; these run per row).
 __device__ __forceinline__ int fdiv(int x, int d, float rcp) {

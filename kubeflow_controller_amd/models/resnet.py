@@ -62,11 +62,11 @@ class Bottleneck(nn.Module):
         st = self.training
         if self.downsample is None:
             y = self.bn1(self.conv1(x, join=join, bn_stats=st), bwd_link=st)
-            # (conv2's output feeds bn2 alone: the same hand-off, ops.conv.Conv2BwdLink, where conv2 is the
+            # (conv2's output feeds bn2 alone: the same hand-off, ops.conv.TailBwdLink of CONV2_BWD, where conv2 is the
             # 64-channel stride-1 3x3 the one-pass kernel covers)
             y = self.bn2(self.conv2(y, bn_stats=st, tail_link=st), bwd_link=st, lazy=st and LAZY_BN2)
             # conv3's output feeds bn3 alone: bn3's backward may leave its input gradient to conv3's
-            # one-pass backward (ops.conv.Conv3BwdLink; identity blocks only)
+            # one-pass backward (ops.conv.TailBwdLink of CONV3_BWD; identity blocks only)
             return self.bn3(self.conv3(y, bn_stats=st, tail_link=st), residual=join.branch(x), bwd_link=st,
                             res_join=join)
         # downsample block: relu(bn3(.) + bn_ds(.)) in ONE apply pass each way

@@ -169,9 +169,9 @@ class _BNActFn(torch.autograd.Function):
         # itself: the backward then skips writing dres (2 of its ~8 bytes per element)
         ctx.res_join = res_join if (training and mb is not None and residual is not None) else None
         ctx.params = (weight, bias)
-        # x = the output of a conv that armed a Conv3BwdLink: this backward may leave dx to it
-        # (training, ReLU with residual bits; the dual / downsample form never gets here)
-        ctx.tail = tail if (tail is not None and training and relu and tail.mask_ok(ss, mb) and tail.take()) else None
+        # x = the output of a conv that armed a TailBwdLink: this backward may leave dx to it
+        # (training, ReLU with the mask source the link's kernel takes; the dual / downsample form never gets here)
+        ctx.tail = tail if (tail is not None and training and relu and tail.rec.mask_ok(ss, mb) and tail.take()) else None
         return y
 
     @staticmethod
@@ -204,7 +204,7 @@ class _BNActFn(torch.autograd.Function):
         if tail is not None and tail.state == "taken" and dres is None and ctx.needs_input_grad[0]:
             # finalize only, into a coef buffer the link owns (the shared one is rewritten by the
             # next BatchNorm backward); dx stays UNWRITTEN: the producing conv's backward forms it
-            # per tile (ops.conv.Conv3BwdLink), or writes it with the apply pass if it cannot
+            # per tile (ops.conv.TailBwdLink), or writes it with the apply pass if it cannot
             tcoef = torch.empty(3 * C, dtype=torch.float32, device=x.device)
             _lib.call("kfa_bn_bwd_finalize_only", _lib.ptr(dy), _lib.ptr(x), _lib.ptr(y), _lib.ptr(weight),
                       _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(slots),
@@ -238,8 +238,11 @@ def bn_act(x, weight, bias, running_mean, running_var, residual=None, training=T
         prestats = False
     link = BnBwdLink() if (bwd_link and training) else None
     lz = LazyBN() if (lazy and training and relu and residual is None and MASK_FROM_X and x.is_cuda) else None
-    # the link the producing conv armed: conv3 -> bn3 (+ residual), or conv2 -> bn2 (no residual)
-    tail = getattr(x, "_kfa_conv3_link" if residual is not None else "_kfa_conv2_link", None) if training else None
+    # the link the producing conv armed, if its kernel is for this form of BN: conv3's takes a BN with a
+    # residual (mask bits), conv2's one without (ops.conv.TailBwd.residual); else it stays armed and unused
+    tail = getattr(x, "_kfa_tail_link", None) if training else None
+    if tail is not None and tail.rec.residual != (residual is not None):
+        tail = None
     y = _BNActFn.apply(x, weight, bias, running_mean, running_var, residual, training, momentum, eps, relu,
                        prestats, link, res_join, lz, tail)
     if link is not None:

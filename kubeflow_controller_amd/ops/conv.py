@@ -126,15 +126,13 @@ _lib.register("kfa_bn_stats_partial", [P, P, _lib.L, I, P])
 _lib.register("kfa_stem_s2d", [P, P, I, I, I, I, I, P])
 _lib.register("kfa_stem_weight_s2d", [P, P, I, I, I, I, P])
 _lib.register("kfa_stem_wgrad_fold", [P, P, I, I, I, I, I, I, P])
-# g x3 mb coef y2 wt dx2 grad | grad_f32 accumulate | part | Nb P Q Ci Co R S stride pad | stats bn_x bn_mean |
-# bn_relu | bn_ss bn_mb | max_blocks | stream
-_lib.register("kfa_conv3_bwd_fused", [P] * 8 + [I, I, P] + [I] * 9 + [P, P, P, I, P, P, I, P])
-_lib.register("kfa_conv3_bwd_part_floats", [I] * 6, _lib.L)
 _lib.register("kfa_bn_bwd_apply_only", [P] * 5 + [_lib.L, I, I, P, P, P])
-# g2 x2 ss2 coef y1 wt dx1 grad | grad_f32 accumulate | part | Nb H W C Co R S stride pad | stats bn_x bn_mean |
-# bn_relu | bn_ss bn_mb | max_blocks | stream
-_lib.register("kfa_conv2_bwd_fused", [P] * 8 + [I, I, P] + [I] * 9 + [P, P, P, I, P, P, I, P])
-_lib.register("kfa_conv2_bwd_part_floats", [I] * 6, _lib.L)
+# the one-pass backward entries (``TailBwd``), one ABI:
+# g x mask coef y wt dx grad | grad_f32 accumulate | part | Nb H W Ci Co R S stride pad | stats bn_x bn_mean |
+# bn_relu | bn_ss bn_mb | max_blocks | stream          (mask: the consuming BN's ReLU bits, or its [scale | shift])
+for _name in ("conv3_bwd", "conv2_bwd"):
+    _lib.register(f"kfa_{_name}_fused", [P] * 8 + [I, I, P] + [I] * 9 + [P, P, P, I, P, P, I, P])
+    _lib.register(f"kfa_{_name}_part_floats", [I] * 6, _lib.L)  # Nb H W Co Ci max_blocks
 
 # Runtime switches (tests compare against the vendor path); env KFA_CONV_IGEMM=0 / KFA_WGRAD=0 disable.
 ENABLED = os.environ.get("KFA_CONV_IGEMM", "1") != "0"
@@ -142,14 +140,6 @@ WGRAD_ENABLED = os.environ.get("KFA_WGRAD", "1") != "0"
 # KFA_CONV_WGRAD_SIDE=1: conv weight gradients on the side stream (ops/streams.py),
 # concurrent with the data-gradient chain (dgrad convs, BatchNorm backward passes)
 WGRAD_SIDE = os.environ.get("KFA_CONV_WGRAD_SIDE", "0") == "1"
-
-
-# One-pass bn3 backward + conv3 dgrad / wgrad for identity bottleneck tails (csrc/kernels/conv3_bwd.hip,
-# ``Conv3BwdLink``); KFA_CONV3_BWD_FUSED=0 keeps apply + dgrad + wgrad + reduce.  Tests flip the attribute.
-CONV3_BWD_FUSED = os.environ.get("KFA_CONV3_BWD_FUSED", "1") != "0"
-# One-pass bn2 backward + conv2 dgrad / wgrad for the 64-channel stride-1 3x3s (csrc/kernels/conv2_bwd.hip,
-# ``Conv2BwdLink``); KFA_CONV2_BWD_FUSED=0 keeps apply + dgrad + wgrad + reduce everywhere.
-CONV2_BWD_FUSED = os.environ.get("KFA_CONV2_BWD_FUSED", "1") != "0"
 
 
 def igemm_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
@@ -577,77 +567,117 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, w: torch.Tensor, stride: int, 
     return dw
 
 
-class Conv3BwdLink:
-    """Hand-off between a bottleneck's conv3 and the bn3 that consumes its output, created in the
-    forward: bn3's backward leaves its input gradient dx3 UNWRITTEN and conv3's backward forms it
-    tile by tile inside ``kfa_conv3_bwd_fused`` (no dx3 tensor is written or re-read).
+class TailBwd:
+    """One one-pass backward kernel: the consuming BatchNorm's backward apply + this conv's dgrad and
+    wgrad in one launch (``kfa_<name>_fused``), routed against ``sep`` (apply pass + dgrad + wgrad +
+    reduce).  Everything the kernels differ in on the host is a field; ``name`` also gives the route
+    kind, the C symbols, the workspace tag and the switch ``KFA_<NAME>_FUSED`` (0 keeps ``sep``
+    everywhere; ``enabled`` is what tests flip)."""
 
-    States: ``armed`` (conv3's forward made it and tagged its output) -> ``taken`` (bn3's forward
-    picked it up: training, ReLU with residual bits, not the dual form) -> ``deferred`` (bn3's
-    backward ran finalize only into ``coef`` and returned ``placeholder``) -> ``done``.  conv3's
-    backward runs the fused kernel iff its ``dy`` IS the placeholder and both gradients are wanted;
-    in every other case :meth:`materialize` first writes dx3 into the placeholder with the ordinary
-    apply pass, and the separate kernels run as before.  Only a conv whose output feeds that BN
-    alone may be armed (the model asks for it: ``conv2d(..., tail_link=True)``)."""
+    def __init__(self, name: str, taps: int, pad: int, mask: str, residual: bool, shape_ok, key):
+        self.name, self.taps, self.pad = name, taps, pad  # R = S = taps; pad: the one padding covered
+        self.mask = mask          # the BN's ReLU mask the kernel takes: "bits" (link.mb) or "ss" (link.ss, no bits)
+        self.residual = residual  # the consuming BN has a residual (bits) or none (ss): bn_act takes the link only then
+        self.shape_ok = shape_ok  # (x_shape, w_shape, stride, pad) -> bool: what the entry covers
+        self.key = key            # (Nb, H, W, Ci, Co) -> route key
+        self.entry, self.part_floats = f"kfa_{name}_fused", f"kfa_{name}_part_floats"
+        self.enabled = os.environ.get(f"KFA_{name.upper()}_FUSED", "1") != "0"
 
-    __slots__ = ("state", "g", "x3", "mb", "ss", "coef", "placeholder", "relu")
+    def mask_ok(self, ss, mb) -> bool:
+        """The BatchNorm's ReLU mask source is the one the fused kernel takes."""
+        return mb is not None if self.mask == "bits" else (ss is not None and mb is None)
 
-    def __init__(self):
-        self.state = "armed"
-        self.g = self.x3 = self.mb = self.ss = self.coef = self.placeholder = None
-        self.relu = True
+    def mask_operand(self, ss, mb):
+        """The entry's third pointer, of a BatchNorm's [scale | shift] and mask bits."""
+        return mb if self.mask == "bits" else ss
 
-    @staticmethod
-    def mask_ok(ss, mb) -> bool:
-        """The BatchNorm's ReLU mask source is the one the fused kernel takes: residual bits."""
-        return mb is not None
+    def fused(self, g, x, mask, coef, y, w, grad, accumulate: bool, bn=None, max_blocks: int = 0, stride: int = 1,
+              pad=None) -> torch.Tensor:
+        """``kfa_<name>_fused``: returns the gradient of the conv's input ``y``; ``grad`` ([Co][R][S][Ci]
+        memory, bf16 / fp32) (+)= dW.  ``g``, ``x``, ``mask``, ``coef``: the consuming BN's output
+        gradient, input, mask source and finalized coefficients; ``bn``: the ``BnBwdLink`` of the
+        BatchNorm whose output ``y`` is (its backward statistics)."""
+        Nb, Ci, H, W = y.shape
+        Co, _, R, S = w.shape
+        dx = torch.empty((Nb, Ci, H, W), dtype=y.dtype, device=y.device, memory_format=torch.channels_last)
+        wt = _transposed_weight(_cl(w), 0, 1, R, 0, 1, S)
+        nfl = getattr(_lib.lib(), self.part_floats)(Nb, H, W, Co, Ci, max_blocks)
+        part = _lib.workspace(max(nfl, 1) * 4, y.device, f"{self.name}_part{_lib.stream() or 0}").view(torch.float32)
+        bn_ws = bn_x = bn_mean = bn_ss = bn_mb = None
+        relu = 0
+        if bn is not None:
+            from .batchnorm import bn_slot_workspace
+            bn_ws = bn_slot_workspace(Ci, y.device)
+            bn_x, bn_mean, bn_ss, bn_mb, relu = bn.x, bn.mean, bn.ss, bn.mb, int(bn.relu)
+        _lib.call(self.entry, _lib.ptr(g), _lib.ptr(x), _lib.ptr(mask), _lib.ptr(coef), _lib.ptr(y), _lib.ptr(wt),
+                  _lib.ptr(dx), _lib.ptr(grad), int(grad.dtype == torch.float32), int(accumulate), _lib.ptr(part),
+                  Nb, H, W, Ci, Co, R, S, stride, self.pad if pad is None else pad, _lib.ptr(bn_ws), _lib.ptr(bn_x),
+                  _lib.ptr(bn_mean), relu, _lib.ptr(bn_ss), _lib.ptr(bn_mb), max_blocks, _lib.stream())
+        if bn is not None:
+            bn.prestats = True
+        return dx
 
-    def take(self) -> bool:
-        """bn3's forward: True once, for an armed link."""
-        if self.state != "armed":
-            return False
-        self.state = "taken"
-        return True
+    def candidates(self, Nb: int, H: int, W: int, Ci: int, Co: int, device) -> tuple:
+        """``([("sep", fn), ("fused", fn)], clean)`` on scratch operands of one shape: the BN's apply pass
+        + the conv's dgrad (with the input BN's backward statistics) + wgrad + reduce, against the
+        one-pass kernel; ``clean()`` zeroes the BatchNorm slots the launches filled.  What the route
+        times when the shape is not in the table, and ``tools/bench_conv_bwd.py``."""
+        cl, R, pad = torch.channels_last, self.taps, self.pad
+        bf = dict(dtype=torch.bfloat16, device=device)
+        g = torch.randn(Nb, Co, H, W, **bf).contiguous(memory_format=cl)
+        x = torch.randn(Nb, Co, H, W, **bf).contiguous(memory_format=cl)
+        y = torch.randn(Nb, Ci, H, W, **bf).contiguous(memory_format=cl)
+        w = (torch.randn(Co, Ci, R, R, **bf) * 0.05).contiguous(memory_format=cl)
+        ss = mb = None  # the one mask source the kernel takes
+        if self.mask == "bits":
+            mb = torch.randint(0, 256, (Nb * H * W * Co // 8,), dtype=torch.uint8, device=device)
+        else:
+            ss = torch.cat([torch.ones(Co, device=device), torch.zeros(Co, device=device)]).contiguous()
+        coef = torch.randn(3 * Co, dtype=torch.float32, device=device) * 0.1
+        dy = torch.empty_like(x)
+        acc = torch.zeros(w.shape, dtype=torch.float32, device=device).contiguous(memory_format=cl)
+        from .batchnorm import BnBwdLink, bn_slot_workspace
+        bn = BnBwdLink()
+        bn.x = torch.randn(Nb, Ci, H, W, **bf).contiguous(memory_format=cl)
+        bn.mean = torch.zeros(Ci, dtype=torch.float32, device=device)
+        bn.ss = torch.ones(2 * Ci, dtype=torch.float32, device=device)
+        bn.relu = True
 
-    def defer(self, g, x3, mb, coef, placeholder, relu=True, ss=None) -> None:
-        """bn3's backward: dx3 = coef . (g * mb, x3, 1) is left to conv3's backward."""
-        if self.state != "taken":
-            raise RuntimeError(f"{type(self).__name__}.defer in state {self.state!r}")
-        self.g, self.x3, self.mb, self.coef, self.placeholder, self.relu = g, x3, mb, coef, placeholder, relu
-        self.ss = ss
-        self.state = "deferred"
+        def clean():  # the timed launches fill the shared slot workspace: leave it zeroed
+            bn_slot_workspace(Ci, device).zero_()
+            bn.prestats = False
 
-    def is_placeholder(self, dy) -> bool:
-        ph = self.placeholder
-        return (self.state == "deferred" and ph is not None and dy is not None and dy.data_ptr() == ph.data_ptr()
-                and dy.shape == ph.shape and dy.stride() == ph.stride() and dy.dtype == ph.dtype)
+        def sep():
+            _lib.call("kfa_bn_bwd_apply_only", _lib.ptr(g), _lib.ptr(x), None, _lib.ptr(coef), _lib.ptr(dy),
+                      Nb * H * W, Co, 1, _lib.ptr(ss), _lib.ptr(mb), _lib.stream())
+            conv_dgrad(dy, w, y.shape, 1, pad, None, bn)
+            wgrad_into(y, dy, acc, Nb, H, W, Ci, H, W, Co, R, R, 1, pad, True)
 
-    def materialize(self) -> None:
-        """The fallback: write dx3 into the placeholder with bn3's ordinary apply pass."""
-        if self.state != "deferred":
-            return
-        C = self.x3.shape[1] if self.x3.dim() == 4 else self.x3.shape[-1]
-        _lib.call("kfa_bn_bwd_apply_only", _lib.ptr(self.g), _lib.ptr(self.x3), None, _lib.ptr(self.coef),
-                  _lib.ptr(self.placeholder), self.x3.numel() // C, C, int(self.relu), _lib.ptr(self.ss),
-                  _lib.ptr(self.mb), _lib.stream())
-        self.clear()
+        def fused():
+            self.fused(g, x, self.mask_operand(ss, mb), coef, y, w, acc, True, bn)
 
-    def clear(self) -> None:
-        self.g = self.x3 = self.mb = self.ss = self.coef = self.placeholder = None
-        self.state = "done"
+        return [("sep", sep), ("fused", fused)], clean
 
+    def route(self, x_shape, w_shape, device) -> bool:
+        """The decision of one shape: ``fused`` against ``sep`` (the default form; the fused kernel
+        must beat it by the usual margin).  From the committed table, else timed once."""
+        from . import routes
+        Nb, Ci, H, W = x_shape
+        Co = w_shape[0]
+        made = None  # the scratch operands exist only if the shape has to be timed
 
-class Conv2BwdLink(Conv3BwdLink):
-    """The same hand-off between a bottleneck's conv2 (3x3 / stride 1, 64 -> 64 channels) and the bn2
-    that consumes its output: bn2's backward runs finalize only and leaves dx2 to
-    ``kfa_conv2_bwd_fused``, which forms its halo image per tile (``x3`` holds bn2's input x2, ``ss``
-    its forward [scale | shift]: the ReLU mask is recomputed from them, there are no mask bits)."""
+        def lazy(i):
+            def run():
+                nonlocal made
+                if made is None:
+                    made = self.candidates(Nb, H, W, Ci, Co, device)
+                made[0][i][1]()
+            return run
 
-    __slots__ = ()
-
-    @staticmethod
-    def mask_ok(ss, mb) -> bool:
-        return ss is not None and mb is None
+        pick = routes.decide(self.name, self.key(Nb, H, W, Ci, Co), device, [("sep", lazy(0)), ("fused", lazy(1))])
+        if made is not None:
+            made[1]()
+        return pick == 1
 
 
 def conv3_bwd_shape_ok(x_shape, w_shape, stride: int, pad: int) -> bool:
@@ -657,95 +687,6 @@ def conv3_bwd_shape_ok(x_shape, w_shape, stride: int, pad: int) -> bool:
     K = Nb * H * W
     return (R == 1 and S == 1 and stride == 1 and pad == 0 and Ci in (64, 128) and Co == 4 * Ci and 0 < K < (1 << 24)
             and K * Co * 2 < (1 << 31))
-
-
-def conv3_bwd_fused(g, x3, mb, coef, y2, w, grad, accumulate: bool, bn=None, max_blocks: int = 0,
-                    stride: int = 1, pad: int = 0) -> torch.Tensor:
-    """``kfa_conv3_bwd_fused``: returns dX2; ``grad`` ([Co][1][1][Ci] memory, bf16 / fp32) (+)= dW.
-    ``bn``: the ``BnBwdLink`` of the BatchNorm whose output ``y2`` is (its backward statistics)."""
-    Nb, Ci, H, W = y2.shape
-    Co, _, R, S = w.shape
-    dx = torch.empty((Nb, Ci, H, W), dtype=y2.dtype, device=y2.device, memory_format=torch.channels_last)
-    wt = _transposed_weight(_cl(w), 0, 1, R, 0, 1, S)
-    nfl = _lib.lib().kfa_conv3_bwd_part_floats(Nb, H, W, Co, Ci, max_blocks)
-    part = _lib.workspace(max(nfl, 1) * 4, y2.device, f"conv3_bwd_part{_lib.stream() or 0}").view(torch.float32)
-    bn_ws = None
-    bn_x = bn_mean = bn_ss = bn_mb = None
-    relu = 0
-    if bn is not None:
-        from .batchnorm import bn_slot_workspace
-        bn_ws = bn_slot_workspace(Ci, y2.device)
-        bn_x, bn_mean, bn_ss, bn_mb, relu = bn.x, bn.mean, bn.ss, bn.mb, int(bn.relu)
-    _lib.call("kfa_conv3_bwd_fused", _lib.ptr(g), _lib.ptr(x3), _lib.ptr(mb), _lib.ptr(coef), _lib.ptr(y2),
-              _lib.ptr(wt), _lib.ptr(dx), _lib.ptr(grad), int(grad.dtype == torch.float32), int(accumulate),
-              _lib.ptr(part), Nb, H, W, Ci, Co, R, S, stride, pad, _lib.ptr(bn_ws), _lib.ptr(bn_x), _lib.ptr(bn_mean),
-              relu, _lib.ptr(bn_ss), _lib.ptr(bn_mb), max_blocks, _lib.stream())
-    if bn is not None:
-        bn.prestats = True
-    return dx
-
-
-def conv3_bwd_candidates(Nb: int, H: int, W: int, Ci: int, Co: int, device) -> tuple:
-    """``([("sep", fn), ("fused", fn)], clean)`` on scratch operands of one shape: bn3's apply pass +
-    conv3's dgrad (with bn2's backward statistics) + wgrad + reduce, against the one-pass kernel;
-    ``clean()`` zeroes the BatchNorm slots the launches filled.  What the ``conv3_bwd`` route times
-    when the shape is not in the table, and ``tools/bench_conv3_bwd.py``."""
-    cl = torch.channels_last
-    bf = dict(dtype=torch.bfloat16, device=device)
-    g = torch.randn(Nb, Co, H, W, **bf).contiguous(memory_format=cl)
-    x3 = torch.randn(Nb, Co, H, W, **bf).contiguous(memory_format=cl)
-    y2 = torch.randn(Nb, Ci, H, W, **bf).contiguous(memory_format=cl)
-    w = (torch.randn(Co, Ci, 1, 1, **bf) * 0.05).contiguous(memory_format=cl)
-    mb = torch.randint(0, 256, (Nb * H * W * Co // 8,), dtype=torch.uint8, device=device)
-    coef = torch.randn(3 * Co, dtype=torch.float32, device=device) * 0.1
-    dx3 = torch.empty_like(x3)
-    acc = torch.zeros(w.shape, dtype=torch.float32, device=device).contiguous(memory_format=cl)
-    from .batchnorm import BnBwdLink
-    bn = BnBwdLink()
-    bn.x = torch.randn(Nb, Ci, H, W, **bf).contiguous(memory_format=cl)
-    bn.mean = torch.zeros(Ci, dtype=torch.float32, device=device)
-    bn.ss = torch.ones(2 * Ci, dtype=torch.float32, device=device)
-    bn.relu = True
-    M = Nb * H * W
-
-    def clean():  # the timed launches fill the shared slot workspace: leave it zeroed
-        from .batchnorm import bn_slot_workspace
-        bn_slot_workspace(Ci, device).zero_()
-        bn.prestats = False
-
-    def sep():
-        _lib.call("kfa_bn_bwd_apply_only", _lib.ptr(g), _lib.ptr(x3), None, _lib.ptr(coef), _lib.ptr(dx3), M, Co, 1,
-                  None, _lib.ptr(mb), _lib.stream())
-        conv_dgrad(dx3, w, y2.shape, 1, 0, None, bn)
-        wgrad_into(y2, dx3, acc, Nb, H, W, Ci, H, W, Co, 1, 1, 1, 0, True)
-
-    def fused():
-        conv3_bwd_fused(g, x3, mb, coef, y2, w, acc, True, bn)
-
-    return [("sep", sep), ("fused", fused)], clean
-
-
-def _conv3_bwd_route(x_shape, w_shape, device) -> bool:
-    """The ``conv3_bwd`` decision of one shape: ``fused`` against ``sep`` (the default form; the
-    fused kernel must beat it by the usual margin).  From the committed table, else timed once."""
-    from . import routes
-    Nb, Ci, H, W = x_shape
-    Co = w_shape[0]
-    key = (Nb, H, W, Ci, Co)
-    made = None  # the scratch operands exist only if the shape has to be timed
-
-    def lazy(i):
-        def run():
-            nonlocal made
-            if made is None:
-                made = conv3_bwd_candidates(Nb, H, W, Ci, Co, device)
-            made[0][i][1]()
-        return run
-
-    pick = routes.decide("conv3_bwd", key, device, [("sep", lazy(0)), ("fused", lazy(1))])
-    if made is not None:
-        made[1]()
-    return pick == 1
 
 
 def conv2_bwd_shape_ok(x_shape, w_shape, stride: int, pad: int) -> bool:
@@ -758,92 +699,71 @@ def conv2_bwd_shape_ok(x_shape, w_shape, stride: int, pad: int) -> bool:
             and (M + 512) * 128 < (1 << 31) and 256 + 2 * (W + 1) + 1 <= 384)
 
 
-def conv2_bwd_fused(g2, x2, ss2, coef, y1, w, grad, accumulate: bool, bn=None, max_blocks: int = 0,
-                    stride: int = 1, pad: int = 1) -> torch.Tensor:
-    """``kfa_conv2_bwd_fused``: returns dX1; ``grad`` ([Co][3][3][Ci] memory, bf16 / fp32) (+)= dW.
-    ``bn``: the ``BnBwdLink`` of the BatchNorm whose output ``y1`` is (its backward statistics)."""
-    Nb, Ci, H, W = y1.shape
-    Co, _, R, S = w.shape
-    dx = torch.empty((Nb, Ci, H, W), dtype=y1.dtype, device=y1.device, memory_format=torch.channels_last)
-    wt = _transposed_weight(_cl(w), 0, 1, R, 0, 1, S)
-    nfl = _lib.lib().kfa_conv2_bwd_part_floats(Nb, H, W, Ci, Co, max_blocks)
-    part = _lib.workspace(max(nfl, 1) * 4, y1.device, f"conv2_bwd_part{_lib.stream() or 0}").view(torch.float32)
-    bn_ws = None
-    bn_x = bn_mean = bn_ss = bn_mb = None
-    relu = 0
-    if bn is not None:
-        from .batchnorm import bn_slot_workspace
-        bn_ws = bn_slot_workspace(Ci, y1.device)
-        bn_x, bn_mean, bn_ss, bn_mb, relu = bn.x, bn.mean, bn.ss, bn.mb, int(bn.relu)
-    _lib.call("kfa_conv2_bwd_fused", _lib.ptr(g2), _lib.ptr(x2), _lib.ptr(ss2), _lib.ptr(coef), _lib.ptr(y1),
-              _lib.ptr(wt), _lib.ptr(dx), _lib.ptr(grad), int(grad.dtype == torch.float32), int(accumulate),
-              _lib.ptr(part), Nb, H, W, Ci, Co, R, S, stride, pad, _lib.ptr(bn_ws), _lib.ptr(bn_x), _lib.ptr(bn_mean),
-              relu, _lib.ptr(bn_ss), _lib.ptr(bn_mb), max_blocks, _lib.stream())
-    if bn is not None:
-        bn.prestats = True
-    return dx
+# bn3 (+ residual: mask bits) -> conv3 of an identity bottleneck tail (csrc/kernels/conv3_bwd.hip)
+CONV3_BWD = TailBwd("conv3_bwd", 1, 0, "bits", True, conv3_bwd_shape_ok, lambda Nb, H, W, Ci, Co: (Nb, H, W, Ci, Co))
+# bn2 (no residual: the mask recomputed from its [scale | shift]) -> a 64-channel stride-1 3x3 conv2
+# (csrc/kernels/conv2_bwd.hip)
+CONV2_BWD = TailBwd("conv2_bwd", 3, 1, "ss", False, conv2_bwd_shape_ok, lambda Nb, H, W, Ci, Co: (Nb, H, W, Ci))
+TAIL_BWDS = (CONV3_BWD, CONV2_BWD)  # the order conv2d tries them in
+conv3_bwd_fused, conv2_bwd_fused = CONV3_BWD.fused, CONV2_BWD.fused  # the direct launches, as tests and tools call them
 
 
-def conv2_bwd_candidates(Nb: int, H: int, W: int, C: int, device) -> tuple:
-    """``([("sep", fn), ("fused", fn)], clean)`` on scratch operands of one shape: bn2's apply pass +
-    conv2's dgrad (with bn1's backward statistics) + wgrad + reduce, against the one-pass kernel;
-    ``clean()`` zeroes the BatchNorm slots the launches filled.  What the ``conv2_bwd`` route times
-    when the shape is not in the table, and ``tools/bench_conv2_bwd.py``."""
-    cl = torch.channels_last
-    bf = dict(dtype=torch.bfloat16, device=device)
-    g2 = torch.randn(Nb, C, H, W, **bf).contiguous(memory_format=cl)
-    x2 = torch.randn(Nb, C, H, W, **bf).contiguous(memory_format=cl)
-    y1 = torch.randn(Nb, C, H, W, **bf).contiguous(memory_format=cl)
-    w = (torch.randn(C, C, 3, 3, **bf) * 0.05).contiguous(memory_format=cl)
-    ss2 = torch.cat([torch.ones(C, device=device), torch.zeros(C, device=device)]).contiguous()
-    coef = torch.randn(3 * C, dtype=torch.float32, device=device) * 0.1
-    dx2 = torch.empty_like(x2)
-    acc = torch.zeros(w.shape, dtype=torch.float32, device=device).contiguous(memory_format=cl)
-    from .batchnorm import BnBwdLink
-    bn = BnBwdLink()
-    bn.x = torch.randn(Nb, C, H, W, **bf).contiguous(memory_format=cl)
-    bn.mean = torch.zeros(C, dtype=torch.float32, device=device)
-    bn.ss = torch.ones(2 * C, dtype=torch.float32, device=device)
-    bn.relu = True
-    M = Nb * H * W
+class TailBwdLink:
+    """Hand-off between a conv with a one-pass backward (``rec``, a ``TailBwd``) and the BatchNorm that
+    consumes its output, created in the forward: the BN's backward leaves its input gradient UNWRITTEN
+    and the conv's backward forms it tile by tile inside ``kfa_<name>_fused`` (no such tensor is
+    written or re-read).
 
-    def clean():  # the timed launches fill the shared slot workspace: leave it zeroed
-        from .batchnorm import bn_slot_workspace
-        bn_slot_workspace(C, device).zero_()
-        bn.prestats = False
+    States: ``armed`` (the conv's forward made it and tagged its output) -> ``taken`` (the BN's forward
+    picked it up: training, ReLU with the mask source and residual form of ``rec``, not the dual form)
+    -> ``deferred`` (the BN's backward ran finalize only into ``coef`` and returned ``placeholder``)
+    -> ``done``.  The conv's backward runs the fused kernel iff its ``dy`` IS the placeholder and both
+    gradients are wanted; in every other case :meth:`materialize` first writes the gradient into the
+    placeholder with the ordinary apply pass, and the separate kernels run as before.  Only a conv
+    whose output feeds that BN alone may be armed (the model asks for it: ``conv2d(..., tail_link=True)``)."""
 
-    def sep():
-        _lib.call("kfa_bn_bwd_apply_only", _lib.ptr(g2), _lib.ptr(x2), None, _lib.ptr(coef), _lib.ptr(dx2), M, C, 1,
-                  _lib.ptr(ss2), None, _lib.stream())
-        conv_dgrad(dx2, w, y1.shape, 1, 1, None, bn)
-        wgrad_into(y1, dx2, acc, Nb, H, W, C, H, W, C, 3, 3, 1, 1, True)
+    __slots__ = ("rec", "state", "g", "x3", "mb", "ss", "coef", "placeholder", "relu")
 
-    def fused():
-        conv2_bwd_fused(g2, x2, ss2, coef, y1, w, acc, True, bn)
+    def __init__(self, rec: TailBwd):
+        self.rec = rec
+        self.state = "armed"
+        self.g = self.x3 = self.mb = self.ss = self.coef = self.placeholder = None
+        self.relu = True
 
-    return [("sep", sep), ("fused", fused)], clean
+    def take(self) -> bool:
+        """The BN's forward: True once, for an armed link."""
+        if self.state != "armed":
+            return False
+        self.state = "taken"
+        return True
 
+    def defer(self, g, x3, mb, coef, placeholder, relu=True, ss=None) -> None:
+        """The BN's backward: dx = coef . (g * mask, x3, 1) is left to the conv's backward (``x3``: the
+        BN's input, ``mb`` / ``ss``: its mask bits / forward [scale | shift])."""
+        if self.state != "taken":
+            raise RuntimeError(f"{type(self).__name__}.defer in state {self.state!r}")
+        self.g, self.x3, self.mb, self.coef, self.placeholder, self.relu = g, x3, mb, coef, placeholder, relu
+        self.ss = ss
+        self.state = "deferred"
 
-def _conv2_bwd_route(x_shape, w_shape, device) -> bool:
-    """The ``conv2_bwd`` decision of one shape: ``fused`` against ``sep`` (the default form; the
-    fused kernel must beat it by the usual margin).  From the committed table, else timed once."""
-    from . import routes
-    Nb, C, H, W = x_shape
-    key = (Nb, H, W, C)
-    made = None  # the scratch operands exist only if the shape has to be timed
+    def is_placeholder(self, dy) -> bool:
+        ph = self.placeholder
+        return (self.state == "deferred" and ph is not None and dy is not None and dy.data_ptr() == ph.data_ptr()
+                and dy.shape == ph.shape and dy.stride() == ph.stride() and dy.dtype == ph.dtype)
 
-    def lazy(i):
-        def run():
-            nonlocal made
-            if made is None:
-                made = conv2_bwd_candidates(Nb, H, W, C, device)
-            made[0][i][1]()
-        return run
+    def materialize(self) -> None:
+        """The fallback: write dx into the placeholder with the BN's ordinary apply pass."""
+        if self.state != "deferred":
+            return
+        C = self.x3.shape[1] if self.x3.dim() == 4 else self.x3.shape[-1]
+        _lib.call("kfa_bn_bwd_apply_only", _lib.ptr(self.g), _lib.ptr(self.x3), None, _lib.ptr(self.coef),
+                  _lib.ptr(self.placeholder), self.x3.numel() // C, C, int(self.relu), _lib.ptr(self.ss),
+                  _lib.ptr(self.mb), _lib.stream())
+        self.clear()
 
-    pick = routes.decide("conv2_bwd", key, device, [("sep", lazy(0)), ("fused", lazy(1))])
-    if made is not None:
-        made[1]()
-    return pick == 1
+    def clear(self) -> None:
+        self.g = self.x3 = self.mb = self.ss = self.coef = self.placeholder = None
+        self.state = "done"
 
 
 class GradJoin:
@@ -948,7 +868,7 @@ class _ConvFn(torch.autograd.Function):
     def forward(ctx, x, w, stride, pad, join, stats, vendor=False, lazy=None, tail=None):
         ctx.save_for_backward(x, w)
         ctx.stride, ctx.pad, ctx.join = stride, pad, join
-        ctx.tail = tail  # Conv3BwdLink: the consuming BatchNorm's backward may leave dy unwritten
+        ctx.tail = tail  # TailBwdLink: the consuming BatchNorm's backward may leave dy unwritten
         ctx.wparam = w  # the Parameter itself (for the direct flat-gradient write)
         ctx.bn_link = getattr(x, "_kfa_bn_link", None)  # x = output of a BatchNorm (see conv_dgrad)
         if ctx.bn_link is not None:
@@ -970,13 +890,12 @@ class _ConvFn(torch.autograd.Function):
             # (dy is unwritten here: the vendor-wgrad tuner is only asked for a decision it already
             # made, never run; the BatchNorm link must carry a mask the fused entry takes)
             bn = ctx.bn_link
-            on = CONV2_BWD_FUSED if isinstance(tail, Conv2BwdLink) else CONV3_BWD_FUSED
-            if (tail.is_placeholder(dy) and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and on
+            if (tail.is_placeholder(dy) and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and tail.rec.enabled
                     and ctx.join is None and not WGRAD_SIDE and wgrad_ok(x, dy, w)
                     and _own_wgrad_decided(x, w, ctx.stride, ctx.pad)
                     and (bn is None or bn.convs != 1 or bn.y is None)):
                 return _ConvFn._backward_fused(ctx, tail, x, w)
-            tail.materialize()  # dx3 into the placeholder (dy, unless dy is a foreign tensor), then as ever
+            tail.materialize()  # the BN's dx into the placeholder (dy, unless dy is a foreign tensor), then as ever
         if ctx.needs_input_grad[0]:
             addend = addend_mask = None
             bn_link = ctx.bn_link if (ctx.bn_link is not None and ctx.bn_link.convs == 1) else None
@@ -1010,19 +929,16 @@ class _ConvFn(torch.autograd.Function):
 
     @staticmethod
     def _backward_fused(ctx, tail, x, w):
-        """bn3's apply + this conv's dgrad + wgrad in one pass over g and x3 (``Conv3BwdLink``)."""
+        """The consuming BN's apply + this conv's dgrad + wgrad in one pass over the BN's g and x (``TailBwd.fused``)."""
         bn_link = ctx.bn_link if (ctx.bn_link is not None and ctx.bn_link.convs == 1) else None
         wparam = ctx.wparam
         target = direct_grad_view(wparam) if wparam is not None else None
         direct = target is not None and target.dtype in (torch.bfloat16, torch.float32) and \
             target.is_contiguous(memory_format=torch.channels_last)
         grad = target if direct else torch.empty_like(w, memory_format=torch.channels_last)
-        if isinstance(tail, Conv2BwdLink):  # bn2's apply + conv2's dgrad + wgrad (``conv2_bwd_fused``)
-            dx = conv2_bwd_fused(tail.g, tail.x3, tail.ss, tail.coef, _cl(x), w, grad, direct, bn_link,
-                                 stride=ctx.stride, pad=ctx.pad)
-        else:
-            dx = conv3_bwd_fused(tail.g, tail.x3, tail.mb, tail.coef, _cl(x), w, grad, direct, bn_link,
-                                 stride=ctx.stride, pad=ctx.pad)
+        rec = tail.rec
+        dx = rec.fused(tail.g, tail.x3, rec.mask_operand(tail.ss, tail.mb), tail.coef, _cl(x), w, grad, direct,
+                       bn_link, stride=ctx.stride, pad=ctx.pad)
         tail.clear()
         if direct:
             notify_grad_ready(wparam)
@@ -1113,8 +1029,8 @@ def conv2d(x, w, stride: int = 1, pad: int = 0, join: "GradJoin | None" = None, 
     for a BN whose finalize runs later than the next BN's (the downsample BN of
     ``bn_act_dual``); True = the shared one.  ``tail_link``: the caller guarantees the output
     feeds one training ``BatchNorm2dAct`` (+ residual + ReLU) and nothing else; for a shape a
-    one-pass backward covers and its route (``conv3_bwd`` / ``conv2_bwd``) picks, the output is
-    tagged with an armed ``Conv3BwdLink`` / ``Conv2BwdLink``."""
+    one-pass backward (``TAIL_BWDS``) covers and its route picks, the output is tagged with an armed
+    ``TailBwdLink`` (``_kfa_tail_link``)."""
     tag = bn_stats if isinstance(bn_stats, str) else "bn_slots"
 
     def slots():  # the BN's slot workspace (fetched only on a path whose epilogue fills it)
@@ -1127,20 +1043,17 @@ def conv2d(x, w, stride: int = 1, pad: int = 0, join: "GradJoin | None" = None, 
         if stats is not None:
             y._kfa_prestats = True
             y._kfa_prestats_tag = tag
-        if isinstance(tail, Conv2BwdLink):
-            y._kfa_conv2_link = tail
-        elif tail is not None:
-            y._kfa_conv3_link = tail
+        if tail is not None:
+            y._kfa_tail_link = tail
         return y
 
-    def armed():  # a Conv3BwdLink / Conv2BwdLink for this conv's backward, or None
+    def armed():  # a TailBwdLink for this conv's backward, or None
         if not (tail_link and join is None and torch.is_grad_enabled() and x.is_cuda):
             return None
         xs, ws = tuple(x.shape), tuple(w.shape)
-        if CONV3_BWD_FUSED and conv3_bwd_shape_ok(xs, ws, stride, pad):
-            return Conv3BwdLink() if _conv3_bwd_route(xs, ws, x.device) else None
-        if CONV2_BWD_FUSED and conv2_bwd_shape_ok(xs, ws, stride, pad):
-            return Conv2BwdLink() if _conv2_bwd_route(xs, ws, x.device) else None
+        for rec in TAIL_BWDS:
+            if rec.enabled and rec.shape_ok(xs, ws, stride, pad):
+                return TailBwdLink(rec) if rec.route(xs, ws, x.device) else None
         return None
 
     lz = getattr(x, "_kfa_lazy", None)

@@ -1,5 +1,5 @@
 """``kfa_conv2_bwd_fused``'s host plan without a GPU: the partial-workspace size, the refusal codes
-(returned before anything is launched), and the ``Conv2BwdLink`` hand-off's mask rule and
+(returned before anything is launched), and the ``TailBwdLink`` hand-off's mask rule and
 materialise fallback with the kernel library stubbed out."""
 import pytest
 import torch
@@ -58,10 +58,10 @@ def test_link_takes_scale_shift_masks_only_and_materializes_with_them(monkeypatc
     monkeypatch.setattr(_lib, "call", lambda name, *a: made.append((name, a)))
     monkeypatch.setattr(_lib, "stream", lambda: 0)
     ss, mb = torch.zeros(16), torch.zeros(18, dtype=torch.uint8)
-    assert convmod.Conv2BwdLink.mask_ok(ss, None)
-    assert not convmod.Conv2BwdLink.mask_ok(None, mb) and not convmod.Conv2BwdLink.mask_ok(None, None)
-    assert convmod.Conv3BwdLink.mask_ok(None, mb) and not convmod.Conv3BwdLink.mask_ok(ss, None)
-    link = convmod.Conv2BwdLink()
+    assert convmod.CONV2_BWD.mask_ok(ss, None)
+    assert not convmod.CONV2_BWD.mask_ok(None, mb) and not convmod.CONV2_BWD.mask_ok(None, None)
+    assert convmod.CONV3_BWD.mask_ok(None, mb) and not convmod.CONV3_BWD.mask_ok(ss, None)
+    link = convmod.TailBwdLink(convmod.CONV2_BWD)
     assert link.take()
     g, x2 = torch.randn(2, 8, 3, 3), torch.randn(2, 8, 3, 3)
     ph = torch.empty_like(x2)

@@ -12,7 +12,7 @@ image border inside one tile), 3x9x7 in one block, 2x16x16 (two exact tiles), 5x
 (three tiles, the last partial: dW carried across tiles, the prefetch past the end), 1x56x56 over
 two blocks (the real W + 1 = 57 halo, 12.25 tiles).
 
-Block level: ``Bottleneck(256, 64)`` at 2x12x12 with ``CONV2_BWD_FUSED`` on and off from the same
+Block level: ``Bottleneck(256, 64)`` at 2x12x12 with ``CONV2_BWD.enabled`` on and off from the same
 seeds, every gradient within ``test_bottleneck_grads_fused_vs_separate``'s tolerances; with conv2's
 weight frozen the link takes the materialise fallback and still matches.
 """
@@ -204,7 +204,7 @@ def test_fused_entry_refuses_other_geometries():
 
 
 def _block_run(blk, x, g, convmod, monkeypatch, on):
-    monkeypatch.setattr(convmod, "CONV2_BWD_FUSED", on)
+    monkeypatch.setattr(convmod.CONV2_BWD, "enabled", on)
     xr = x.clone().requires_grad_()
     y = blk(xr)
     y.backward(g)
@@ -233,21 +233,21 @@ def test_bottleneck_grads_fused_vs_separate(freeze_conv2, monkeypatch):
     blk2 = copy.deepcopy(blk)
     x = torch.randn(2, cin, 12, 12, device=d).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
     g = torch.randn(2, cin, 12, 12, device=d).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-    monkeypatch.setattr(convmod, "_conv2_bwd_route", lambda *a, **k: True)   # the route says fused
-    monkeypatch.setattr(convmod, "_conv3_bwd_route", lambda *a, **k: False)  # conv3: the separate path both times
+    monkeypatch.setattr(convmod.CONV2_BWD, "route", lambda *a, **k: True)   # the route says fused
+    monkeypatch.setattr(convmod.CONV3_BWD, "route", lambda *a, **k: False)  # conv3: the separate path both times
     calls = {"fused": 0, "materialize": 0}
-    real_fused, real_mat = convmod.conv2_bwd_fused, convmod.Conv2BwdLink.materialize
+    real_fused, real_mat = convmod.TailBwd.fused, convmod.TailBwdLink.materialize
 
-    def fused(*a, **k):
-        calls["fused"] += 1
-        return real_fused(*a, **k)
+    def fused(self, *a, **k):  # (counted for conv2's record only)
+        calls["fused"] += self is convmod.CONV2_BWD
+        return real_fused(self, *a, **k)
 
     def materialize(self):
-        calls["materialize"] += self.state == "deferred"
+        calls["materialize"] += self.state == "deferred" and self.rec is convmod.CONV2_BWD
         return real_mat(self)
 
-    monkeypatch.setattr(convmod, "conv2_bwd_fused", fused)
-    monkeypatch.setattr(convmod.Conv2BwdLink, "materialize", materialize)
+    monkeypatch.setattr(convmod.TailBwd, "fused", fused)
+    monkeypatch.setattr(convmod.TailBwdLink, "materialize", materialize)
     ya, ga, pa = _block_run(blk, x, g, convmod, monkeypatch, True)
     assert convmod.conv2_bwd_shape_ok((2, mid, 12, 12), (mid, mid, 3, 3), 1, 1)
     assert calls == {"fused": int(not freeze_conv2), "materialize": int(freeze_conv2)}

@@ -1,4 +1,4 @@
-"""``ops.conv.Conv3BwdLink``: the hand-off's state machine, on the CPU with the kernel library
+"""``ops.conv.TailBwdLink`` (of ``CONV3_BWD``): the hand-off's state machine, on the CPU with the kernel library
 stubbed out (no GPU call): placeholder identity, the materialise fallback on a foreign ``dy`` or
 when a gradient is not wanted, and no arming in eval mode or on the CPU."""
 import types
@@ -18,7 +18,7 @@ def calls(monkeypatch):
 
 
 def _deferred():
-    link = convmod.Conv3BwdLink()
+    link = convmod.TailBwdLink(convmod.CONV3_BWD)
     assert link.state == "armed" and link.take() and not link.take()  # picked up once
     g, x3 = torch.randn(2, 8, 3, 3), torch.randn(2, 8, 3, 3)
     ph = torch.empty_like(x3)
@@ -28,7 +28,7 @@ def _deferred():
 
 
 def test_defer_needs_a_taken_link():
-    link = convmod.Conv3BwdLink()
+    link = convmod.TailBwdLink(convmod.CONV3_BWD)
     with pytest.raises(RuntimeError):
         link.defer(None, None, None, None, None)
 
@@ -61,7 +61,7 @@ def test_backward_takes_the_fused_entry_only_for_the_placeholder(calls, monkeypa
     x, w = torch.randn(2, 4, 3, 3), torch.randn(8, 4, 1, 1)
     monkeypatch.setattr(convmod, "wgrad_ok", lambda *a: True)
     monkeypatch.setattr(convmod, "TUNE", False)  # (with the tuner on, only a decision already made counts)
-    monkeypatch.setattr(convmod, "CONV3_BWD_FUSED", True)
+    monkeypatch.setattr(convmod.CONV3_BWD, "enabled", True)
     fused = []
     monkeypatch.setattr(convmod._ConvFn, "_backward_fused", staticmethod(lambda ctx, tail, x, w: fused.append(tail) or "fused"))
     link, ph = _deferred()
@@ -82,18 +82,18 @@ def test_backward_takes_the_fused_entry_only_for_the_placeholder(calls, monkeypa
 
     # the switch turned off between forward and backward: the fallback too
     del calls[:]
-    monkeypatch.setattr(convmod, "CONV3_BWD_FUSED", False)
+    monkeypatch.setattr(convmod.CONV3_BWD, "enabled", False)
     link, ph = _deferred()
     convmod._ConvFn.backward(_ctx(link, x, w, (False, False)), ph)
     assert calls == ["kfa_bn_bwd_apply_only"] and len(fused) == 1
 
 
 def test_no_arming_on_cpu_or_in_eval(calls, monkeypatch):
-    monkeypatch.setattr(convmod, "_conv3_bwd_route", lambda *a, **k: True)
+    monkeypatch.setattr(convmod.CONV3_BWD, "route", lambda *a, **k: True)
     x = torch.randn(1, 64, 4, 4, requires_grad=True)
     w = torch.randn(256, 64, 1, 1, requires_grad=True)
     y = convmod.conv2d(x, w, tail_link=True)
-    assert getattr(y, "_kfa_conv3_link", None) is None and calls == []
+    assert getattr(y, "_kfa_tail_link", None) is None and calls == []
     # a CPU bottleneck in training runs plain PyTorch end to end
     from kubeflow_controller_amd.models.resnet import Bottleneck
     blk = Bottleneck(256, 64, 1)

@@ -179,7 +179,7 @@ def test_fused_entry_refuses_other_geometries():
 
 
 def _block_run(blk, x, g, convmod, monkeypatch, on):
-    monkeypatch.setattr(convmod, "CONV3_BWD_FUSED", on)
+    monkeypatch.setattr(convmod.CONV3_BWD, "enabled", on)
     xr = x.clone().requires_grad_()
     y = blk(xr)
     y.backward(g)
@@ -209,20 +209,20 @@ def test_bottleneck_grads_fused_vs_separate(cin, mid, freeze_conv3, monkeypatch)
     blk2 = copy.deepcopy(blk)
     x = torch.randn(2, cin, 12, 12, device=d).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
     g = torch.randn(2, cin, 12, 12, device=d).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-    monkeypatch.setattr(convmod, "_conv3_bwd_route", lambda *a, **k: True)  # the route says fused
+    monkeypatch.setattr(convmod.CONV3_BWD, "route", lambda *a, **k: True)  # the route says fused
     calls = {"fused": 0, "materialize": 0}
-    real_fused, real_mat = convmod.conv3_bwd_fused, convmod.Conv3BwdLink.materialize
+    real_fused, real_mat = convmod.TailBwd.fused, convmod.TailBwdLink.materialize
 
-    def fused(*a, **k):
-        calls["fused"] += 1
-        return real_fused(*a, **k)
+    def fused(self, *a, **k):  # (counted for conv3's record only)
+        calls["fused"] += self is convmod.CONV3_BWD
+        return real_fused(self, *a, **k)
 
     def materialize(self):
-        calls["materialize"] += self.state == "deferred"
+        calls["materialize"] += self.state == "deferred" and self.rec is convmod.CONV3_BWD
         return real_mat(self)
 
-    monkeypatch.setattr(convmod, "conv3_bwd_fused", fused)
-    monkeypatch.setattr(convmod.Conv3BwdLink, "materialize", materialize)
+    monkeypatch.setattr(convmod.TailBwd, "fused", fused)
+    monkeypatch.setattr(convmod.TailBwdLink, "materialize", materialize)
     ya, ga, pa = _block_run(blk, x, g, convmod, monkeypatch, True)
     covered = convmod.conv3_bwd_shape_ok((2, mid, 12, 12), (cin, mid, 1, 1), 1, 0)
     assert calls == {"fused": int(covered and not freeze_conv3), "materialize": int(covered and freeze_conv3)}
