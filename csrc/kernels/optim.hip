@@ -5,7 +5,7 @@
 // tensor.  Mixed precision: the fp32 master copy is updated and the bf16
 // compute copy (if any) is rewritten in the same pass; grads may be bf16
 // (the all-reduced bucket) or fp32.  8 elements per lane, 16-B loads for
-// bf16, 2x16-B for fp32.  LAMB and the global-norm clip coefficient (further down) add
+// bf16, 2x16-B for fp32.  LAMB, LARS and the global-norm clip coefficient (further down) add
 // per-tensor and whole-gradient norms as fixed-order segmented reductions over the same
 // buffers; every scalar they produce stays in device memory.
 #include "common.h"
@@ -320,6 +320,101 @@ __global__ __launch_bounds__(256) void lamb_stage2_kernel(float* __restrict__ w,
   }
 }
 
+// ---------------------------------------------------------------- LARS
+// Momentum SGD whose update of tensor t is scaled by a layer-wise rate (You, Gitman, Ginsburg 2017):
+//   lambda_t = trust * |w_t| / (|g~_t| + wd * |w_t| + eps),  g~ = g * gscale * clip (1 when either norm is 0)
+//   d = lambda_t * (g~ + wd * w),  mom = momentum * mom + d,  w -= lr * (nesterov ? d + momentum * mom : mom)
+// over the chunk table above.  The norms pass reads g and w once for both per-tensor norms and
+// leaves the g^2 partials where clip_finish_kernel takes its own, so a clipped step reads the
+// gradient once for the global norm and the per-tensor ones.
+
+// per-chunk sums of w^2 and of the (unscaled) gradient's squares: wpart[c], gpart[c]
+template <bool GBF16>
+__global__ __launch_bounds__(256) void lars_norms_kernel(const float* __restrict__ w, const void* __restrict__ g,
+                                                         const long* __restrict__ chunks, int nchunks,
+                                                         float* __restrict__ wpart, float* __restrict__ gpart) {
+  __shared__ float sh[4][2];
+  for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const long start = chunks[3 * c + 1], len = chunks[3 * c + 2];
+    float sw = 0.f, sg = 0.f;
+    for (long o = (long)threadIdx.x * 8; o < len; o += 256 * 8) {
+      const long i = start + o, valid = len - o;
+      float gr[8], p[8];
+      load_grad8<GBF16>(g, i, gr, 1.f);
+      load8(w + i, p);
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        sw = j < valid ? fmaf(p[j], p[j], sw) : sw;
+        sg = j < valid ? fmaf(gr[j], gr[j], sg) : sg;
+      }
+    }
+    block_sum2(sw, sg, sh);
+    if (threadIdx.x == 0) {
+      wpart[c] = sw;
+      gpart[c] = sg;
+    }
+  }
+}
+
+// ratio[t] = lambda_t from the partials of tensor t's chunks [tens[2t], tens[2t] + tens[2t + 1]); |g~_t| is
+// |gscale * dcoef[0]| * sqrt(sum g^2) (dcoef == nullptr: no clipping).  One wave per tensor, summing as
+// lamb_ratio_kernel does: lane l takes chunks l, l + 64, ... in order, then the xor tree.
+__global__ __launch_bounds__(64) void lars_ratio_kernel(const float* __restrict__ wpart,
+                                                        const float* __restrict__ gpart,
+                                                        const long* __restrict__ tens, float* __restrict__ ratio,
+                                                        float gscale, const float* __restrict__ dcoef, float trust,
+                                                        float wd, float eps) {
+  const long first = tens[2 * blockIdx.x], count = tens[2 * blockIdx.x + 1];
+  float sw = 0.f, sg = 0.f;
+  for (long k = threadIdx.x; k < count; k += 64) {
+    sw += wpart[first + k];
+    sg += gpart[first + k];
+  }
+  sw = wave_sum(sw);
+  sg = wave_sum(sg);
+  if (threadIdx.x == 0) {
+    if (dcoef) gscale *= dcoef[0];
+    const float wn = sqrtf(sw), gn = fabsf(gscale) * sqrtf(sg);
+    ratio[blockIdx.x] = (wn > 0.f && gn > 0.f) ? trust * wn / (gn + wd * wn + eps) : 1.f;
+  }
+}
+
+// The update, chunk by chunk, with ratio[tensor id] from the chunk row (ratio == nullptr: lambda = 1 and
+// no multiply, which makes the arithmetic sgd_kernel's at dampening 0, operation for operation).  mom
+// starts at 0, so the first step needs no flag.  Lanes past a tensor's length are written back as loaded.
+template <bool GBF16>
+__global__ __launch_bounds__(256) void lars_apply_kernel(float* __restrict__ w, bf16_t* __restrict__ wb,
+                                                         const void* __restrict__ g, float* __restrict__ mom,
+                                                         const long* __restrict__ chunks, int nchunks,
+                                                         const float* __restrict__ ratio, float lr, float momentum,
+                                                         float wd, int nesterov, float gscale,
+                                                         const float* __restrict__ dcoef) {
+  if (dcoef) gscale *= dcoef[0];
+  for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const long start = chunks[3 * c + 1], len = chunks[3 * c + 2];
+    const float lam = ratio ? ratio[chunks[3 * c]] : 1.f;
+    for (long o = (long)threadIdx.x * 8; o < len; o += 256 * 8) {
+      const long i = start + o, valid = len - o;
+      float gr[8], p[8], m[8];
+      load_grad8<GBF16>(g, i, gr, gscale);
+      load8(w + i, p);
+      load8(mom + i, m);
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        if (j < valid) {
+          float d = fmaf(wd, p[j], gr[j]);
+          if (ratio) d *= lam;
+          m[j] = fmaf(momentum, m[j], d);
+          p[j] = fmaf(-lr, nesterov ? fmaf(momentum, m[j], d) : m[j], p[j]);
+        }
+      }
+      store8(mom + i, m);
+      store8(w + i, p);
+      if (wb) *reinterpret_cast<uint4*>(wb + i) = pack8(p);
+    }
+  }
+}
+
 int chunk_grid(int nchunks) { return nchunks < 2048 ? nchunks : 2048; }
 
 int grid_for(long n8) {
@@ -439,6 +534,44 @@ KFA_API int kfa_lamb_stage2(float* w, bf16_t* wb, const float* m, const float* v
   if (nchunks <= 0 || !dbc) return nchunks ? -1 : 0;
   hipLaunchKernelGGL(lamb_stage2_kernel, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, wb, m, v, chunks, nchunks,
                      ratio, lr, eps, wd, dbc);
+  return kfa_status();
+}
+
+// LARS norms: wpart[nchunks], gpart[nchunks] = per-chunk sums of w^2 and of g^2 (g unscaled; gpart may
+// point into the buffer kfa_clip_finish reduces).  Chunk table as for kfa_chunk_sumsq.
+KFA_API int kfa_lars_norms(const float* w, const void* g, int g_is_bf16, const long* chunks, int nchunks,
+                           float* wpart, float* gpart, hipStream_t s) {
+  if (nchunks <= 0 || !wpart || !gpart) return nchunks ? -1 : 0;
+  if (g_is_bf16)
+    hipLaunchKernelGGL(lars_norms_kernel<true>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, g, chunks, nchunks,
+                       wpart, gpart);
+  else
+    hipLaunchKernelGGL(lars_norms_kernel<false>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, g, chunks, nchunks,
+                       wpart, gpart);
+  return kfa_status();
+}
+
+// tens: ntens device rows of two longs: first chunk, chunk count.  ratio[ntens] = the layer-wise rates;
+// dcoef: nullptr or the device clip coefficient.
+KFA_API int kfa_lars_ratio(const float* wpart, const float* gpart, const long* tens, int ntens, float* ratio,
+                           float gscale, const float* dcoef, float trust, float wd, float eps, hipStream_t s) {
+  if (ntens <= 0) return ntens ? -1 : 0;
+  hipLaunchKernelGGL(lars_ratio_kernel, dim3(ntens), dim3(64), 0, s, wpart, gpart, tens, ratio, gscale, dcoef, trust,
+                     wd, eps);
+  return kfa_status();
+}
+
+// LARS update: mom, w (and wb, if any) updated with ratio[tensor id] (nullptr: 1, plain momentum SGD)
+KFA_API int kfa_lars_apply(float* w, bf16_t* wb, const void* g, int g_is_bf16, float* mom, const long* chunks,
+                           int nchunks, const float* ratio, float lr, float momentum, float wd, int nesterov,
+                           float gscale, const float* dcoef, hipStream_t s) {
+  if (nchunks <= 0 || !mom) return nchunks ? -1 : 0;
+  if (g_is_bf16)
+    hipLaunchKernelGGL(lars_apply_kernel<true>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, wb, g, mom, chunks,
+                       nchunks, ratio, lr, momentum, wd, nesterov, gscale, dcoef);
+  else
+    hipLaunchKernelGGL(lars_apply_kernel<false>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, wb, g, mom, chunks,
+                       nchunks, ratio, lr, momentum, wd, nesterov, gscale, dcoef);
   return kfa_status();
 }
 

@@ -1,12 +1,13 @@
-"""Fused SGD(+momentum, weight decay, nesterov), Adam/AdamW and LAMB over flat
-parameter groups, and global-norm gradient clipping for the latter two —
+"""Fused SGD(+momentum, weight decay, nesterov), Adam/AdamW, LAMB and LARS over flat
+parameter groups, and global-norm gradient clipping for the latter three —
 ``csrc/kernels/optim.hip``.
 
-One kernel launch per optimizer space per step (LAMB: two passes and one small
-launch for its per-tensor trust ratios; clipping: one more read of the gradient,
-every norm and coefficient kept on the device); the gradient average over
-data-parallel ranks (``1/world``) and any loss scale are folded into
-``grad_scale`` so no separate scaling pass runs.  A space is a whole flat group
+One kernel launch per optimizer space per step (LAMB and LARS: two passes and one
+small launch for their per-tensor trust ratios; clipping: one more read of the
+gradient, which LARS shares with its norms pass, every norm and coefficient kept on
+the device); the gradient average over data-parallel ranks (``1/world``) and any
+loss scale are folded into ``grad_scale`` so no separate scaling pass runs.  A
+space is a whole flat group
 or the compact parameter-server / ZeRO shard a rank owns (``parallel/ps.py``):
 the optimizer state is allocated at the space's size, so an owner holds state
 only for what it owns.
@@ -34,6 +35,9 @@ _lib.register("kfa_clip_finish", [P, I, F, F, P, P])
 _lib.register("kfa_lamb_stage1", [P, P, I, P, P, P, I, P, F, F, F, F, F, P, P, P])
 _lib.register("kfa_lamb_ratio", [P, P, I, P, P])
 _lib.register("kfa_lamb_stage2", [P, P, P, P, P, I, P, F, F, F, P, P])
+_lib.register("kfa_lars_norms", [P, P, I, P, I, P, P, P])
+_lib.register("kfa_lars_ratio", [P, P, P, I, P, F, P, F, F, F, P])
+_lib.register("kfa_lars_apply", [P, P, P, I, P, P, I, P, F, F, F, I, F, P, P])
 
 # elements per chunk of the fixed-order segmented reductions (LAMB norms, the clip norm):
 # one block reduces one chunk, 8 vectors of 8 elements per lane (kfa_chunk_sumsq: <= 65536)
@@ -143,7 +147,7 @@ class _FusedBase:
 
     def scratch_bytes(self) -> int:
         """Bytes of the norm reductions' tables and partial sums: per chunk and per
-        tensor, never per element (0 without LAMB or clipping)."""
+        tensor, never per element (0 without LAMB, LARS or clipping)."""
         bufs = [self._clip, getattr(self, "_gpart", None), *getattr(self, "_part", []), *getattr(self, "_ratio", [])]
         for t in self._tabs or []:
             bufs += [t.chunks, t.tens]
@@ -405,5 +409,128 @@ class FusedLAMB(_AdamMoments):
                 if wn > 0 and un > 0:
                     r = wn / un
             w.add_(u, alpha=-lr * r)
+        if s.wb is not None:
+            s.wb.copy_(s.w)
+
+
+class FusedLARS(_FusedBase):
+    """LARS (You, Gitman, Ginsburg, 2017): momentum SGD whose update of tensor ``t`` of
+    a space is scaled by a layer-wise rate.  With g~ = g * grad_scale * clip
+
+        lambda_t = trust * |w_t| / (|g~_t| + wd * |w_t| + eps)   (1 when either norm is 0)
+        d   = lambda_t * (g~ + wd * w)
+        mom = momentum * mom + d
+        w  -= lr * (d + momentum * mom  if nesterov else  mom)
+
+    with ``lambda_t`` on the spaces named in ``adapt_groups`` (default: the decay
+    groups, i.e. ``"weights"``) and exactly 1 elsewhere; ``wd`` follows
+    ``decay_groups``.  ``lr`` multiplies what the momentum buffer gives, which is
+    ``FusedSGD``'s and ``torch.optim.SGD``'s convention; the paper folds ``lr`` into
+    the buffer, so the two differ whenever ``lr`` changes between steps.  ``mom``
+    starts at 0 and there is no dampening, so no step is special.
+
+    An adapting space takes one pass for its norms (g and w read once, per-chunk sums
+    of w^2 and g^2), one small launch for the rates and the update pass; the other
+    spaces take the update pass alone.  With ``max_grad_norm`` the g^2 partials are
+    also the global norm's (the spaces that do not adapt add theirs with one read of
+    their gradient), so a clipped step reads no gradient twice for a norm.  Every sum
+    runs in a fixed order and every scalar stays on the device: a step is
+    bit-repeatable and replays from a HIP graph.  The step is not elementwise: there
+    is no ranged ``update``, and every space needs its tensors' ``segments``.
+
+    ``FusedLARS(adapt_groups=())`` is momentum SGD with global-norm clipping, which
+    ``FusedSGD`` does not take: without ``max_grad_norm``, and with the norm under
+    it, the step is ``FusedSGD(dampening=0)``'s bit for bit."""
+
+    def __init__(self, spaces, lr=0.1, momentum=0.9, weight_decay=5e-5, trust=0.001, eps=1e-8, nesterov=False,
+                 decay_groups=None, adapt_groups=None, max_grad_norm=None):
+        for s in _as_spaces(spaces):
+            if s.segments is None:
+                raise ValueError(f"FusedLARS: optimizer space {s.name!r} has no per-tensor segments "
+                                 "(a sharded layout); LARS needs whole tensors for its trust ratios")
+        super().__init__(spaces, lr, weight_decay, decay_groups, max_grad_norm)
+        self.momentum = momentum
+        self.trust = trust
+        self.eps = eps
+        self.nesterov = nesterov
+        self.adapt_groups = set(adapt_groups) if adapt_groups is not None else set(self.decay_groups)
+        self.mom = [torch.zeros(s.numel, dtype=torch.float32, device=s.device) for s in self.spaces]
+        self._ratio = [torch.ones(len(s.segments), dtype=torch.float32, device=s.device) if self._adapts(s) else None
+                       for s in self.spaces]
+        self._part = []  # GPU: per chunk of an adapting space, the sum of w^2
+        if self.spaces and self.spaces[0].device.type == "cuda":
+            self._part = [torch.zeros(t.nchunks, dtype=torch.float32, device=s.device) if self._adapts(s) else None
+                          for s, t in zip(self.spaces, self._tables())]
+            if self._clip is None:  # the g^2 partials, in the layout _clip_scalar gives them when clipping
+                self._gpart = torch.zeros(sum(t.nchunks for t in self._tables()), dtype=torch.float32,
+                                          device=self.spaces[0].device)
+
+    def _adapts(self, s: OptSpace) -> bool:
+        return s.name in self.adapt_groups or not s.name
+
+    @property
+    def trust_ratios(self) -> List[Optional[torch.Tensor]]:
+        """Per space, the rates ``lambda_t`` of the last step: one tensor on the space's
+        device with an entry per tensor, or ``None`` for a space that does not adapt.
+        For logging: the step writes them, nothing may write them from outside."""
+        return list(self._ratio)
+
+    @torch.no_grad()
+    def step(self, grad_scale: float = 1.0, lr: Optional[float] = None) -> None:
+        self.step_count += 1
+        lr = self.lr if lr is None else lr
+        if not self.spaces:
+            return
+        if self._cpu(self.spaces[0]):
+            if self._clip is not None:
+                self._clip_scalar(grad_scale)
+            for si in range(len(self.spaces)):
+                self._cpu_step(si, grad_scale, lr)
+            return
+        tabs, stream = self._tables(), _lib.stream()
+        off, gparts = 0, []
+        for si, (s, t) in enumerate(zip(self.spaces, tabs)):
+            g = s.grad
+            gpart = self._gpart.data_ptr() + 4 * off
+            if self._ratio[si] is not None:
+                _lib.call("kfa_lars_norms", _lib.ptr(s.w), _lib.ptr(g), int(g.dtype == torch.bfloat16),
+                          _lib.ptr(t.chunks), t.nchunks, _lib.ptr(self._part[si]), gpart, stream)
+            elif self._clip is not None:  # its share of the global norm
+                _lib.call("kfa_chunk_sumsq", _lib.ptr(g), int(g.dtype == torch.bfloat16), _lib.ptr(t.chunks),
+                          t.nchunks, gpart, stream)
+            gparts.append(gpart)
+            off += t.nchunks
+        if self._clip is not None:
+            _lib.call("kfa_clip_finish", _lib.ptr(self._gpart), off, grad_scale, self.max_grad_norm,
+                      _lib.ptr(self._clip), stream)
+        for si, (s, t) in enumerate(zip(self.spaces, tabs)):
+            g, ratio, wd = s.grad, self._ratio[si], self._wd(s)
+            if ratio is not None:
+                _lib.call("kfa_lars_ratio", _lib.ptr(self._part[si]), gparts[si], _lib.ptr(t.tens), t.ntens,
+                          _lib.ptr(ratio), grad_scale, self._dcoef(), self.trust, wd, self.eps, stream)
+            _lib.call("kfa_lars_apply", _lib.ptr(s.w), _lib.ptr(s.wb), _lib.ptr(g), int(g.dtype == torch.bfloat16),
+                      _lib.ptr(self.mom[si]), _lib.ptr(t.chunks), t.nchunks, _lib.ptr(ratio), lr, self.momentum, wd,
+                      int(self.nesterov), grad_scale, self._dcoef(), stream)
+
+    def _cpu_step(self, si: int, grad_scale: float, lr: float) -> None:
+        s = self.spaces[si]
+        wd, ratio = self._wd(s), self._ratio[si]
+        gr = s.grad
+        for k, (a, n) in enumerate(s.segments):
+            w, mom = s.w[a:a + n], self.mom[si][a:a + n]
+            d = gr[a:a + n].float() * grad_scale
+            if self._clip is not None:
+                d = d * self._clip[1]
+            lam = 1.0
+            if ratio is not None:
+                wn, gn = float(w.double().norm()), float(d.double().norm())  # fp32 sums drift at 1e6 elements
+                if wn > 0 and gn > 0:
+                    lam = self.trust * wn / (gn + wd * wn + self.eps)
+                ratio[k] = lam
+            d = d.add(w, alpha=wd)
+            if ratio is not None:
+                d = d * lam
+            mom.mul_(self.momentum).add_(d)
+            w.add_(d + self.momentum * mom if self.nesterov else mom, alpha=-lr)
         if s.wb is not None:
             s.wb.copy_(s.w)

@@ -89,33 +89,38 @@ class Engine:
     the end of each HIP Function's backward; autograd's AccumulateGrad after the
     producing node), and the side stream waits for the main stream at each
     bucket; the next step's forward waits for the side stream.  Off for
-    ``optimizer="lamb"`` and with ``max_grad_norm``, which take norms over the
-    whole gradient.
+    ``optimizer="lamb"`` / ``"lars"`` and with ``max_grad_norm``, which take
+    norms over the whole gradient.
 
-    ``optimizer``: ``"sgd"``, ``"adam"`` / ``"adamw"`` or ``"lamb"``
-    (``ops/optim.py``).  ``max_grad_norm`` (Adam, LAMB): clip the gradient to
+    ``optimizer``: ``"sgd"``, ``"adam"`` / ``"adamw"``, ``"lamb"`` or ``"lars"``
+    (``ops/optim.py``).  ``"lars"`` is momentum SGD with a layer-wise rate on the
+    weights: ``momentum``, ``nesterov`` and ``trust_coefficient`` are its
+    parameters.  ``max_grad_norm`` (Adam, LAMB, LARS): clip the gradient to
     that global L2 norm; the norm and the coefficient stay on the device
-    (``opt.last_grad_norm``), so the step still captures as a HIP graph.  Both
-    need the data-parallel all-reduce layout (``ps == 0`` or one rank)."""
+    (``opt.last_grad_norm``), so the step still captures as a HIP graph.  LAMB,
+    LARS and clipping need the data-parallel all-reduce layout (``ps == 0`` or
+    one rank)."""
 
     def __init__(self, model: torch.nn.Module, loss_fn: Callable, *, optimizer: str = "sgd", lr: float = 0.1,
                  momentum: float = 0.9, weight_decay: float = 5e-5, betas=(0.9, 0.999), eps: float = 1e-8,
                  compute_dtype=torch.bfloat16, bucket_mb: float = 32.0, dist_info: Optional[DistInfo] = None,
                  channels_last: bool = True, ps: int = 0, ps_placement: str = "ps",
                  grad_reduce_dtype: Optional[torch.dtype] = torch.float32, comm=None,
-                 opt_overlap: Optional[bool] = None, max_grad_norm: Optional[float] = None):
-        from ..ops.optim import FusedAdam, FusedLAMB, FusedSGD
+                 opt_overlap: Optional[bool] = None, max_grad_norm: Optional[float] = None,
+                 nesterov: bool = False, trust_coefficient: float = 0.001):
+        from ..ops.optim import FusedAdam, FusedLAMB, FusedLARS, FusedSGD
         from ..parallel.ddp import GradSync, broadcast_params
 
         self.info = dist_info or DistInfo()
-        # LAMB's per-tensor norms and the clip's global norm are taken over whole gradients
-        whole_grad = optimizer == "lamb" or max_grad_norm is not None
+        # LAMB's / LARS's per-tensor norms and the clip's global norm are taken over whole gradients
+        whole_grad = optimizer in ("lamb", "lars") or max_grad_norm is not None
         if whole_grad and ps > 0 and self.info.world > 1:  # before any collective: every rank raises
-            raise ValueError("optimizer='lamb' / max_grad_norm need the whole gradient on every rank (data-parallel "
-                             "all-reduce, ps=0): in the sharded parameter-server layouts a rank holds only its shard, "
-                             "and norms across shards are not built")
+            raise ValueError("optimizer='lamb' / 'lars' / max_grad_norm need the whole gradient on every rank "
+                             "(data-parallel all-reduce, ps=0): in the sharded parameter-server layouts a rank holds "
+                             "only its shard, and norms across shards are not built")
         if optimizer == "sgd" and max_grad_norm is not None:
-            raise ValueError("max_grad_norm: gradient clipping is not built for optimizer='sgd' (use adam or lamb)")
+            raise ValueError("max_grad_norm: gradient clipping is not built for optimizer='sgd' "
+                             "(use adam, lamb or lars)")
         if self.info.world > 1:  # per-shape tuner decisions are broadcast from rank 0 (ops/conv._agree)
             from ..ops import conv as _conv
             _conv.set_lockstep(True)
@@ -156,13 +161,16 @@ class Engine:
         elif optimizer == "lamb":
             self.opt = FusedLAMB(spaces, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                  max_grad_norm=max_grad_norm)
+        elif optimizer == "lars":
+            self.opt = FusedLARS(spaces, lr=lr, momentum=momentum, weight_decay=weight_decay, trust=trust_coefficient,
+                                 eps=eps, nesterov=nesterov, max_grad_norm=max_grad_norm)
         else:
             raise ValueError(f"unknown optimizer {optimizer!r}")
         self.steps = 0
         self._graph = None  # (hipGraph, captured inputs, captured loss) once capture() ran
         if opt_overlap is None:
             opt_overlap = os.environ.get("KFA_OPT_OVERLAP", "0") == "1" and self.info.device.type == "cuda"
-        # off at world > 1 (the buckets run their all-reduce) and for LAMB / clipping: the
+        # off at world > 1 (the buckets run their all-reduce) and for LAMB / LARS / clipping: the
         # norms need every gradient of the step before the first element is updated
         self.opt_overlap = bool(opt_overlap) and self.info.world == 1 and not self.sharded and not whole_grad
         self._opt_open = False
@@ -220,8 +228,8 @@ class Engine:
         Every kernel argument is frozen at capture, so what changes per step
         must live in device memory or not change at all: lr / momentum /
         decay are constants, Adam's / LAMB's step count and bias corrections
-        are advanced on the device (``kfa_adam_bc``), LAMB's trust ratios and the
-        clip coefficient are computed and read there.  A model whose forward takes
+        are advanced on the device (``kfa_adam_bc``), LAMB's and LARS's trust ratios
+        and the clip coefficient are computed and read there.  A model whose forward takes
         per-step host values (dropout seeds) says so with
         ``graph_capturable = False``.  Collectives stay eager (world > 1): RCCL
         work issued from backward hooks is not replayed through this path.
@@ -294,7 +302,7 @@ class Engine:
         for name in ("mom", "m", "v"):
             for b in getattr(self.opt, name, None) or []:
                 n += b.numel() * b.element_size() if b is not None else 0
-        n += self.opt.scratch_bytes()  # LAMB / clipping: per-chunk partial sums, nothing per element
+        n += self.opt.scratch_bytes()  # LAMB / LARS / clipping: per-chunk partial sums, nothing per element
         if self.sharded:
             n += sum(t.numel() * t.element_size() for t in self.sync.gshard)
         else:

@@ -209,20 +209,20 @@ def _async_mode(spec: ClusterSpec, args) -> bool:
 
 
 def _check_whole_gradient(spec: ClusterSpec, args, async_mode: bool) -> None:
-    """LAMB's per-tensor norms and the clip's global norm need every worker to hold the
+    """LAMB's and LARS's per-tensor norms and the clip's global norm need every worker to hold the
     whole reduced gradient: the all-reduce layout (or one replica).  Raises ValueError for
     the async PS mode, whose PS tasks keep Adam / SGD, and for the sharded collective layouts."""
-    if args.optimizer != "lamb" and args.max_grad_norm is None:
+    if args.optimizer not in ("lamb", "lars") and args.max_grad_norm is None:
         return
     if args.optimizer == "sgd":
-        raise ValueError("--max_grad_norm: gradient clipping is not built for --optimizer sgd (use adam or lamb)")
+        raise ValueError("--max_grad_norm: gradient clipping is not built for --optimizer sgd (use adam, lamb or lars)")
     if async_mode:
-        raise ValueError("--optimizer lamb / --max_grad_norm are not available in the async parameter-server "
+        raise ValueError("--optimizer lamb / lars / --max_grad_norm are not available in the async parameter-server "
                          "mode: its PS tasks apply Adam or SGD per pushed gradient (parallel/async_ps.py); "
                          "run the job without PS tasks (all-reduce)")
     if spec.ps and spec.num_workers > 1 and not spec.is_local:
-        raise ValueError("--optimizer lamb / --max_grad_norm need the whole gradient on every worker: with PS tasks "
-                         "the collective mode shards it over the owners; run the job without PS tasks (all-reduce)")
+        raise ValueError("--optimizer lamb / lars / --max_grad_norm need the whole gradient on every worker: with PS "
+                         "tasks the collective mode shards it over the owners; run the job without PS tasks (all-reduce)")
 
 
 # ------------------------------------------------------------------ roles
@@ -445,7 +445,7 @@ def run_worker(spec: ClusterSpec, args) -> int:
                     bucket_mb=args.bucket_mb, dist_info=DistInfo(rank, world, 0, device),
                     channels_last=model.__class__.__name__ == "ResNet", ps=num_ps, ps_placement=args.ps_placement,
                     grad_reduce_dtype=None if args.grad_reduce == "bf16" else torch.float32,
-                    max_grad_norm=args.max_grad_norm)
+                    max_grad_norm=args.max_grad_norm, trust_coefficient=args.trust_coefficient)
     model = engine.model
     resumed = engine.restore(args.model_dir) if args.model_dir else 0
     if resumed:
@@ -577,12 +577,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--train_steps", type=int, default=200)
     ap.add_argument("--batch_size", type=int, default=100)
     ap.add_argument("--learning_rate", type=float, default=0.01)
-    ap.add_argument("--optimizer", default="adam", choices=["adam", "sgd", "lamb"],
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "sgd", "lamb", "lars"],
                     help="lamb: Adam moments with per-tensor trust ratios (the large-batch BERT recipe); "
-                         "collective / local modes only")
+                         "lars: momentum SGD with a layer-wise rate on the weights (the large-batch ResNet "
+                         "recipe; takes --momentum and --trust_coefficient); both collective / local modes only")
     ap.add_argument("--max_grad_norm", type=float, default=None,
-                    help="clip the gradient to this global L2 norm before the update (adam, lamb; "
+                    help="clip the gradient to this global L2 norm before the update (adam, lamb, lars; "
                          "collective / local modes only)")
+    ap.add_argument("--trust_coefficient", type=float, default=0.001,
+                    help="--optimizer lars: the coefficient of the layer-wise rate")
     ap.add_argument("--momentum", type=float, default=0.0)
     ap.add_argument("--weight_decay", type=float, default=0.0)
     ap.add_argument("--hidden_units", type=int, default=100)
