@@ -147,23 +147,6 @@ __global__ void f32_to_bf16_kernel(const float* __restrict__ a, bf16_t* __restri
   }
 }
 
-// sum of squares for grad-norm clipping: per-block partials -> atomicAdd
-template <bool GBF16>
-__global__ __launch_bounds__(256) void sumsq_kernel(const void* __restrict__ g, long n8, float* __restrict__ out) {
-  float acc = 0.f;
-  for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < n8; v += (long)gridDim.x * blockDim.x) {
-    float gr[8];
-    load_grad8<GBF16>(g, v * 8, gr, 1.f);
-#pragma unroll
-    for (int j = 0; j < 8; j++) acc = fmaf(gr[j], gr[j], acc);
-  }
-  acc = wave_sum(acc);
-  __shared__ float sh[4];
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, sh[0] + sh[1] + sh[2] + sh[3]);
-}
-
 // ---------------------------------------------------------------- LAMB + global-norm clipping
 // Norms are segmented reductions over the flat buffer in a FIXED order (no float atomics,
 // no zero-fill): the host cuts every tensor into chunks of at most CHUNK elements, a chunk
@@ -422,20 +405,31 @@ int grid_for(long n8) {
   return (int)(b < 2048 ? (b < 1 ? 1 : b) : 2048);
 }
 
+// The guard of an entry over a flat bucket: n a multiple of 8 (buckets are padded) and every operand it
+// cannot do without; the entry returns -1 otherwise.
+bool whole_vectors(long n, bool operands = true) { return n % 8 == 0 && operands; }
+
+// The guard of an entry over a chunk (or tensor) table of `count` rows: 1 = launch; otherwise the entry's
+// return value: 0 for an empty table (nothing to do, whatever the operands), -1 for a negative count or a
+// missing operand.
+int table_guard(int count, bool operands = true) { return count > 0 && operands ? 1 : (count ? -1 : 0); }
+
+// One launch of a kernel templated on the gradient's dtype: the <true> instantiation for bf16 gradients,
+// the <false> one for fp32, the arguments written once.
+template <class... P, class... A>
+void launch_g(void (*bf16)(P...), void (*f32)(P...), int g_is_bf16, int grid, hipStream_t s, A... args) {
+  hipLaunchKernelGGL(g_is_bf16 ? bf16 : f32, dim3(grid), dim3(256), 0, s, args...);
+}
+
 }  // namespace
 
 // n must be a multiple of 8 (flat buckets are padded); pointers 16-B aligned.
 KFA_API int kfa_sgd_step(float* w, bf16_t* wb, const void* g, int g_is_bf16, float* mom, long n, float lr,
                          float momentum, float dampening, float wd, int nesterov, float gscale, int first,
                          hipStream_t s) {
-  if (n % 8) return -1;
-  const long n8 = n / 8;
-  if (g_is_bf16)
-    hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid_for(n8)), dim3(256), 0, s, w, wb, g, mom, n8, lr, momentum,
-                       dampening, wd, nesterov, gscale, first);
-  else
-    hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid_for(n8)), dim3(256), 0, s, w, wb, g, mom, n8, lr, momentum,
-                       dampening, wd, nesterov, gscale, first);
+  if (!whole_vectors(n)) return -1;
+  launch_g(sgd_kernel<true>, sgd_kernel<false>, g_is_bf16, grid_for(n / 8), s, w, wb, g, mom, n / 8, lr, momentum,
+           dampening, wd, nesterov, gscale, first);
   return kfa_status();
 }
 
@@ -443,30 +437,21 @@ KFA_API int kfa_sgd_step(float* w, bf16_t* wb, const void* g, int g_is_bf16, flo
 KFA_API int kfa_adam_step(float* w, bf16_t* wb, const void* g, int g_is_bf16, float* m, float* v, long n, float lr,
                           float b1, float b2, float eps, float wd, float bc1, float bc2, float gscale, const float* dbc,
                           hipStream_t s) {
-  if (n % 8) return -1;
-  const long n8 = n / 8;
-  if (g_is_bf16)
-    hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_for(n8)), dim3(256), 0, s, w, wb, g, m, v, n8, lr, b1, b2, eps,
-                       wd, bc1, bc2, gscale, dbc);
-  else
-    hipLaunchKernelGGL(adam_kernel<false>, dim3(grid_for(n8)), dim3(256), 0, s, w, wb, g, m, v, n8, lr, b1, b2, eps,
-                       wd, bc1, bc2, gscale, dbc);
+  if (!whole_vectors(n)) return -1;
+  launch_g(adam_kernel<true>, adam_kernel<false>, g_is_bf16, grid_for(n / 8), s, w, wb, g, m, v, n / 8, lr, b1, b2, eps,
+           wd, bc1, bc2, gscale, dbc);
   return kfa_status();
 }
 
-KFA_API int kfa_adam_bc(int* t, float* bc, float b1, float b2, hipStream_t s) {
-  hipLaunchKernelGGL(adam_bc_kernel, dim3(1), dim3(64), 0, s, t, bc, b1, b2, -1);
-  return kfa_status();
-}
-
-// the same, the device count first set to `seed` when seed >= 0 (eager steps, resumes)
-KFA_API int kfa_adam_bc_seed(int* t, float* bc, float b1, float b2, int seed, hipStream_t s) {
+// t += 1 and bc = (1 - b1^t, 1 - b2^t) on the device; seed >= 0 (eager steps, resumes): the device
+// count is first set to `seed`; seed < 0 (a captured step): it advances from what the device holds
+KFA_API int kfa_adam_bc(int* t, float* bc, float b1, float b2, int seed, hipStream_t s) {
   hipLaunchKernelGGL(adam_bc_kernel, dim3(1), dim3(64), 0, s, t, bc, b1, b2, seed);
   return kfa_status();
 }
 
 KFA_API int kfa_f32_to_bf16(const float* a, bf16_t* b, long n, hipStream_t s) {
-  if (n % 8) return -1;
+  if (!whole_vectors(n)) return -1;
   hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for(n / 8)), dim3(256), 0, s, a, b, n / 8);
   return kfa_status();
 }
@@ -475,14 +460,9 @@ KFA_API int kfa_f32_to_bf16(const float* a, bf16_t* b, long n, hipStream_t s) {
 KFA_API int kfa_adam_step_clip(float* w, bf16_t* wb, const void* g, int g_is_bf16, float* m, float* v, long n,
                                float lr, float b1, float b2, float eps, float wd, float gscale, const float* dbc,
                                const float* dcoef, hipStream_t s) {
-  if (n % 8 || !dbc || !dcoef) return -1;
-  const long n8 = n / 8;
-  if (g_is_bf16)
-    hipLaunchKernelGGL(adam_clip_kernel<true>, dim3(grid_for(n8)), dim3(256), 0, s, w, wb, g, m, v, n8, lr, b1, b2,
-                       eps, wd, gscale, dbc, dcoef);
-  else
-    hipLaunchKernelGGL(adam_clip_kernel<false>, dim3(grid_for(n8)), dim3(256), 0, s, w, wb, g, m, v, n8, lr, b1, b2,
-                       eps, wd, gscale, dbc, dcoef);
+  if (!whole_vectors(n, dbc && dcoef)) return -1;
+  launch_g(adam_clip_kernel<true>, adam_clip_kernel<false>, g_is_bf16, grid_for(n / 8), s, w, wb, g, m, v, n / 8, lr,
+           b1, b2, eps, wd, gscale, dbc, dcoef);
   return kfa_status();
 }
 
@@ -490,11 +470,9 @@ KFA_API int kfa_adam_step_clip(float* w, bf16_t* wb, const void* g, int g_is_bf1
 // readable up to the next multiple of 8 past start + length, length <= 65536.  part[nchunks].
 KFA_API int kfa_chunk_sumsq(const void* g, int g_is_bf16, const long* chunks, int nchunks, float* part,
                             hipStream_t s) {
-  if (nchunks <= 0) return nchunks ? -1 : 0;
-  if (g_is_bf16)
-    hipLaunchKernelGGL(chunk_sumsq_kernel<true>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, g, chunks, nchunks, part);
-  else
-    hipLaunchKernelGGL(chunk_sumsq_kernel<false>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, g, chunks, nchunks, part);
+  if (const int go = table_guard(nchunks); go <= 0) return go;
+  launch_g(chunk_sumsq_kernel<true>, chunk_sumsq_kernel<false>, g_is_bf16, chunk_grid(nchunks), s, g, chunks, nchunks,
+           part);
   return kfa_status();
 }
 
@@ -507,23 +485,19 @@ KFA_API int kfa_clip_finish(const float* part, int nparts, float gscale, float m
 }
 
 // LAMB stage 1: m, v updated; part[2 * nchunks] = per-chunk sums of w^2, u^2 or nullptr.
-// dbc: the device pair of kfa_adam_bc_seed; dcoef: nullptr or the device clip coefficient.
+// dbc: the device pair of kfa_adam_bc; dcoef: nullptr or the device clip coefficient.
 KFA_API int kfa_lamb_stage1(const float* w, const void* g, int g_is_bf16, float* m, float* v, const long* chunks,
                             int nchunks, float* part, float b1, float b2, float eps, float wd, float gscale,
                             const float* dbc, const float* dcoef, hipStream_t s) {
-  if (nchunks <= 0 || !dbc) return nchunks ? -1 : 0;
-  if (g_is_bf16)
-    hipLaunchKernelGGL(lamb_stage1_kernel<true>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, g, m, v, chunks,
-                       nchunks, part, b1, b2, eps, wd, gscale, dbc, dcoef);
-  else
-    hipLaunchKernelGGL(lamb_stage1_kernel<false>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, g, m, v, chunks,
-                       nchunks, part, b1, b2, eps, wd, gscale, dbc, dcoef);
+  if (const int go = table_guard(nchunks, dbc); go <= 0) return go;
+  launch_g(lamb_stage1_kernel<true>, lamb_stage1_kernel<false>, g_is_bf16, chunk_grid(nchunks), s, w, g, m, v, chunks,
+           nchunks, part, b1, b2, eps, wd, gscale, dbc, dcoef);
   return kfa_status();
 }
 
 // tens: ntens device rows of two longs: first chunk, chunk count.  ratio[ntens].
 KFA_API int kfa_lamb_ratio(const float* part, const long* tens, int ntens, float* ratio, hipStream_t s) {
-  if (ntens <= 0) return ntens ? -1 : 0;
+  if (const int go = table_guard(ntens); go <= 0) return go;
   hipLaunchKernelGGL(lamb_ratio_kernel, dim3(ntens), dim3(64), 0, s, part, tens, ratio);
   return kfa_status();
 }
@@ -531,7 +505,7 @@ KFA_API int kfa_lamb_ratio(const float* part, const long* tens, int ntens, float
 // LAMB stage 2: w (and wb, if any) updated with ratio[tensor id] (nullptr: 1) from the m, v of stage 1
 KFA_API int kfa_lamb_stage2(float* w, bf16_t* wb, const float* m, const float* v, const long* chunks, int nchunks,
                             const float* ratio, float lr, float eps, float wd, const float* dbc, hipStream_t s) {
-  if (nchunks <= 0 || !dbc) return nchunks ? -1 : 0;
+  if (const int go = table_guard(nchunks, dbc); go <= 0) return go;
   hipLaunchKernelGGL(lamb_stage2_kernel, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, wb, m, v, chunks, nchunks,
                      ratio, lr, eps, wd, dbc);
   return kfa_status();
@@ -541,13 +515,9 @@ KFA_API int kfa_lamb_stage2(float* w, bf16_t* wb, const float* m, const float* v
 // point into the buffer kfa_clip_finish reduces).  Chunk table as for kfa_chunk_sumsq.
 KFA_API int kfa_lars_norms(const float* w, const void* g, int g_is_bf16, const long* chunks, int nchunks,
                            float* wpart, float* gpart, hipStream_t s) {
-  if (nchunks <= 0 || !wpart || !gpart) return nchunks ? -1 : 0;
-  if (g_is_bf16)
-    hipLaunchKernelGGL(lars_norms_kernel<true>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, g, chunks, nchunks,
-                       wpart, gpart);
-  else
-    hipLaunchKernelGGL(lars_norms_kernel<false>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, g, chunks, nchunks,
-                       wpart, gpart);
+  if (const int go = table_guard(nchunks, wpart && gpart); go <= 0) return go;
+  launch_g(lars_norms_kernel<true>, lars_norms_kernel<false>, g_is_bf16, chunk_grid(nchunks), s, w, g, chunks, nchunks,
+           wpart, gpart);
   return kfa_status();
 }
 
@@ -555,7 +525,7 @@ KFA_API int kfa_lars_norms(const float* w, const void* g, int g_is_bf16, const l
 // dcoef: nullptr or the device clip coefficient.
 KFA_API int kfa_lars_ratio(const float* wpart, const float* gpart, const long* tens, int ntens, float* ratio,
                            float gscale, const float* dcoef, float trust, float wd, float eps, hipStream_t s) {
-  if (ntens <= 0) return ntens ? -1 : 0;
+  if (const int go = table_guard(ntens); go <= 0) return go;
   hipLaunchKernelGGL(lars_ratio_kernel, dim3(ntens), dim3(64), 0, s, wpart, gpart, tens, ratio, gscale, dcoef, trust,
                      wd, eps);
   return kfa_status();
@@ -565,22 +535,8 @@ KFA_API int kfa_lars_ratio(const float* wpart, const float* gpart, const long* t
 KFA_API int kfa_lars_apply(float* w, bf16_t* wb, const void* g, int g_is_bf16, float* mom, const long* chunks,
                            int nchunks, const float* ratio, float lr, float momentum, float wd, int nesterov,
                            float gscale, const float* dcoef, hipStream_t s) {
-  if (nchunks <= 0 || !mom) return nchunks ? -1 : 0;
-  if (g_is_bf16)
-    hipLaunchKernelGGL(lars_apply_kernel<true>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, wb, g, mom, chunks,
-                       nchunks, ratio, lr, momentum, wd, nesterov, gscale, dcoef);
-  else
-    hipLaunchKernelGGL(lars_apply_kernel<false>, dim3(chunk_grid(nchunks)), dim3(256), 0, s, w, wb, g, mom, chunks,
-                       nchunks, ratio, lr, momentum, wd, nesterov, gscale, dcoef);
-  return kfa_status();
-}
-
-// out must be zeroed by the caller (accumulates)
-KFA_API int kfa_sumsq(const void* g, int g_is_bf16, long n, float* out, hipStream_t s) {
-  if (n % 8) return -1;
-  if (g_is_bf16)
-    hipLaunchKernelGGL(sumsq_kernel<true>, dim3(grid_for(n / 8)), dim3(256), 0, s, g, n / 8, out);
-  else
-    hipLaunchKernelGGL(sumsq_kernel<false>, dim3(grid_for(n / 8)), dim3(256), 0, s, g, n / 8, out);
+  if (const int go = table_guard(nchunks, mom); go <= 0) return go;
+  launch_g(lars_apply_kernel<true>, lars_apply_kernel<false>, g_is_bf16, chunk_grid(nchunks), s, w, wb, g, mom, chunks,
+           nchunks, ratio, lr, momentum, wd, nesterov, gscale, dcoef);
   return kfa_status();
 }

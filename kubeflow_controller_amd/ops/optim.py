@@ -25,10 +25,8 @@ from ..parallel.flat import FlatGroup
 P, L, I, F = _lib.P, _lib.L, _lib.I, _lib.F
 _lib.register("kfa_sgd_step", [P, P, P, I, P, L, F, F, F, F, I, F, I, P])
 _lib.register("kfa_adam_step", [P, P, P, I, P, P, L, F, F, F, F, F, F, F, F, P, P])
-_lib.register("kfa_adam_bc", [P, P, F, F, P])
-_lib.register("kfa_adam_bc_seed", [P, P, F, F, I, P])
+_lib.register("kfa_adam_bc", [P, P, F, F, I, P])
 _lib.register("kfa_f32_to_bf16", [P, P, L, P])
-_lib.register("kfa_sumsq", [P, I, L, P, P])
 _lib.register("kfa_adam_step_clip", [P, P, P, I, P, P, L, F, F, F, F, F, F, P, P, P])
 _lib.register("kfa_chunk_sumsq", [P, I, P, I, P, P])
 _lib.register("kfa_clip_finish", [P, I, F, F, P, P])
@@ -112,15 +110,39 @@ class _ChunkTable:
         self.tens = torch.tensor(tens, dtype=torch.int64, device=s.device).reshape(-1, 2)
 
 
+# The trainers' rules, once: WHOLE_GRAD take per-tensor norms and max_grad_norm a global one, so every
+# rank must hold the whole gradient (all-reduce layout); CLIPS are the optimizers that take max_grad_norm.
+WHOLE_GRAD = ("lamb", "lars")
+CLIPS = ("adam", "adamw", "lamb", "lars")
+
+
+def needs_whole_grad(optimizer: str, max_grad_norm: Optional[float]) -> bool:
+    return optimizer in WHOLE_GRAD or max_grad_norm is not None
+
+
+def _garg(g: torch.Tensor) -> Tuple[int, int]:
+    """A gradient as the kernels take it: (device address, is_bf16)."""
+    return g.data_ptr(), int(g.dtype == torch.bfloat16)
+
+
 class _FusedBase:
+    """The spaces, their one device (``_gpu``: the kernels run, else the CPU arithmetic), the chunk
+    tables and the clip scalar.  ``g2_partials``: the subclass reads ``_gpart`` itself, clipping or not."""
+
     def __init__(self, spaces: Sequence, lr: float, weight_decay: float,
-                 decay_groups: Optional[Sequence[str]] = None, max_grad_norm: Optional[float] = None):
+                 decay_groups: Optional[Sequence[str]] = None, max_grad_norm: Optional[float] = None,
+                 g2_partials: bool = False):
         self.spaces: List[OptSpace] = _as_spaces(spaces)
+        self.device = self.spaces[0].device if self.spaces else torch.device("cpu")
+        self._gpu = self.device.type == "cuda"
         self.lr = lr
         self.weight_decay = weight_decay
         self.decay_groups = set(decay_groups) if decay_groups is not None else {"weights"}
         self.step_count = 0
         self._tabs: Optional[List[_ChunkTable]] = None
+        # LAMB / LARS: per space, the per-chunk partial sums and the per-tensor trust ratios
+        self._part: List[Optional[torch.Tensor]] = []
+        self._ratio: List[Optional[torch.Tensor]] = []
         # global-norm clipping: (pre-clip norm, coefficient) stay on the device; the step
         # kernels read the coefficient there, so no step waits for the host
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
@@ -128,17 +150,18 @@ class _FusedBase:
         if self.max_grad_norm is not None:
             if not self.max_grad_norm > 0:
                 raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm!r}")
-            dev = self.spaces[0].device if self.spaces else torch.device("cpu")
-            self._clip = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
-            if dev.type == "cuda":  # one partial per chunk, every space's in one buffer
-                self._gpart = torch.zeros(sum(t.nchunks for t in self._tables()), dtype=torch.float32, device=dev)
+            self._clip = torch.tensor([0.0, 1.0], dtype=torch.float32, device=self.device)
+        self._dcoef = self._clip.data_ptr() + 4 if self._clip is not None else None  # the coefficient's address
+        # GPU: one g^2 partial per chunk, every space's in one buffer, each space's chunks contiguous
+        self._gpart: Optional[torch.Tensor] = None
+        self._gaddr: List[int] = []  # per space, the device address of its partials in _gpart
+        if self._gpu and (self._clip is not None or g2_partials):
+            counts = [t.nchunks for t in self._tables()]
+            self._gpart = torch.zeros(sum(counts), dtype=torch.float32, device=self.device)
+            self._gaddr = [self._gpart.data_ptr() + 4 * sum(counts[:si]) for si in range(len(counts))]
 
     def _wd(self, s: OptSpace) -> float:
         return self.weight_decay if s.name in self.decay_groups or not s.name else 0.0
-
-    @staticmethod
-    def _cpu(s: OptSpace) -> bool:
-        return not s.w.is_cuda
 
     def _tables(self) -> List[_ChunkTable]:
         if self._tabs is None:
@@ -148,7 +171,7 @@ class _FusedBase:
     def scratch_bytes(self) -> int:
         """Bytes of the norm reductions' tables and partial sums: per chunk and per
         tensor, never per element (0 without LAMB, LARS or clipping)."""
-        bufs = [self._clip, getattr(self, "_gpart", None), *getattr(self, "_part", []), *getattr(self, "_ratio", [])]
+        bufs = [self._clip, self._gpart, *self._part, *self._ratio]
         for t in self._tabs or []:
             bufs += [t.chunks, t.tens]
         return sum(b.numel() * b.element_size() for b in bufs if b is not None)
@@ -160,19 +183,22 @@ class _FusedBase:
         logging: reading it waits for the device, so the caller decides when."""
         return self._clip[0] if self._clip is not None else None
 
+    def _g2_partials(self, si: int, stream: int) -> None:
+        """GPU: leave the per-chunk sums of g^2 of space ``si`` at ``_gaddr[si]``."""
+        t = self._tabs[si]
+        _lib.call("kfa_chunk_sumsq", *_garg(self.spaces[si].grad), _lib.ptr(t.chunks), t.nchunks, self._gaddr[si],
+                  stream)
+
     @torch.no_grad()
-    def _clip_scalar(self, grad_scale: float) -> None:
+    def _clip_scalar(self, grad_scale: float, stream: Optional[int] = None) -> None:
         """norm = grad_scale * |g| over every space and coef = min(1, max / (norm + 1e-6))
         (``torch.nn.utils.clip_grad_norm_``) into ``_clip``, in a fixed summation order."""
-        if self._clip.is_cuda:
-            off = 0
-            for s, t in zip(self.spaces, self._tables()):
-                g = s.grad
-                _lib.call("kfa_chunk_sumsq", _lib.ptr(g), int(g.dtype == torch.bfloat16), _lib.ptr(t.chunks),
-                          t.nchunks, self._gpart.data_ptr() + 4 * off, _lib.stream())
-                off += t.nchunks
-            _lib.call("kfa_clip_finish", _lib.ptr(self._gpart), off, grad_scale, self.max_grad_norm,
-                      _lib.ptr(self._clip), _lib.stream())
+        if self._gpu:
+            stream = _lib.stream() if stream is None else stream
+            for si in range(len(self.spaces)):
+                self._g2_partials(si, stream)
+            _lib.call("kfa_clip_finish", _lib.ptr(self._gpart), self._gpart.numel(), grad_scale, self.max_grad_norm,
+                      _lib.ptr(self._clip), stream)
             return
         total = torch.zeros((), dtype=torch.float32)
         for s in self.spaces:
@@ -183,23 +209,19 @@ class _FusedBase:
         self._clip[0] = norm
         self._clip[1] = (self.max_grad_norm / (norm + 1e-6)).clamp(max=1.0)
 
-    def _dcoef(self) -> Optional[int]:
-        """Device address of the clip coefficient (None: no clipping)."""
-        return self._clip.data_ptr() + 4 if self._clip is not None else None
+    def _cpu_grad(self, g: torch.Tensor, grad_scale: float) -> torch.Tensor:
+        """The CPU paths' gradient slice in fp32: scaled, and clipped by the coefficient of ``_clip``."""
+        d = g.float() * grad_scale
+        return d * self._clip[1] if self._clip is not None else d
 
-    def grad_norm(self, grad_scale: float = 1.0) -> torch.Tensor:
-        """L2 norm of the gradient this rank holds (its shard in the sharded layouts)."""
-        out = torch.zeros(1, dtype=torch.float32, device=self.spaces[0].device)
-        for s in self.spaces:
-            g = s.grad
-            if g.numel() == 0:
-                continue
-            if g.is_cuda:
-                _lib.call("kfa_sumsq", _lib.ptr(g), int(g.dtype == torch.bfloat16), g.numel(),
-                          _lib.ptr(out), _lib.stream())
-            else:
-                out += g.float().pow(2).sum()
-        return out.sqrt() * grad_scale
+    @torch.no_grad()
+    def step(self, grad_scale: float = 1.0, lr: Optional[float] = None) -> None:
+        """The whole step of an elementwise optimizer (SGD, Adam): every space as one range."""
+        self.begin_step()
+        if self._clip is not None:
+            self._clip_scalar(grad_scale)
+        for si, s in enumerate(self.spaces):
+            self.update(si, 0, s.numel, grad_scale, lr)
 
 
 class FusedSGD(_FusedBase):
@@ -231,7 +253,7 @@ class FusedSGD(_FusedBase):
         s, mom = self.spaces[si], self.mom[si]
         w, wb, gr = s.w[a:b], (s.wb[a:b] if s.wb is not None else None), s.grad[a:b]
         mom = mom[a:b] if mom is not None else None
-        if self._cpu(s):
+        if not self._gpu:
             d = gr.float() * grad_scale + self._wd(s) * w
             if mom is not None:
                 if self._first:
@@ -243,16 +265,8 @@ class FusedSGD(_FusedBase):
             if wb is not None:
                 wb.copy_(w)
             return
-        _lib.call("kfa_sgd_step", _lib.ptr(w), _lib.ptr(wb), _lib.ptr(gr), int(gr.dtype == torch.bfloat16),
-                  _lib.ptr(mom), b - a, lr, self.momentum, self.dampening, self._wd(s), int(self.nesterov),
-                  grad_scale, self._first, _lib.stream())
-
-    @torch.no_grad()
-    def step(self, grad_scale: float = 1.0, lr: Optional[float] = None) -> None:
-        self.begin_step()
-        for si, s in enumerate(self.spaces):
-            self.update(si, 0, s.numel, grad_scale, lr)
-
+        _lib.call("kfa_sgd_step", _lib.ptr(w), _lib.ptr(wb), *_garg(gr), _lib.ptr(mom), b - a, lr, self.momentum,
+                  self.dampening, self._wd(s), int(self.nesterov), grad_scale, self._first, _lib.stream())
 
 class _AdamMoments(_FusedBase):
     """The state Adam and LAMB share: the moments ``m`` / ``v`` (the names
@@ -266,19 +280,17 @@ class _AdamMoments(_FusedBase):
         self.v = [torch.zeros(s.numel, dtype=torch.float32, device=s.device) for s in self.spaces]
         # GPU: the step count t and (1 - b1^t, 1 - b2^t) live on the device, advanced
         # by kfa_adam_bc inside the step, so the step replays from a HIP graph
-        dev = self.spaces[0].device if self.spaces else torch.device("cpu")
-        self._t = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
-        self._bc = torch.ones(2, dtype=torch.float32, device=dev) if dev.type == "cuda" else None
+        self._t = torch.zeros(1, dtype=torch.int32, device=self.device) if self._gpu else None
+        self._bc = torch.ones(2, dtype=torch.float32, device=self.device) if self._gpu else None
 
     def begin_step(self) -> None:
         """Open one optimizer step whose updates are issued per range (``update``):
         the step count and the bias corrections advance once, here."""
-        if self._t is not None:
+        if self._gpu:
             # eager steps (and resumes) re-seed the device count inside the same launch; a
             # captured step advances it on the device (graph replay)
             seed = -1 if torch.cuda.is_current_stream_capturing() else self.step_count
-            _lib.call("kfa_adam_bc_seed", _lib.ptr(self._t), _lib.ptr(self._bc), self.b1, self.b2, seed,
-                      _lib.stream())
+            _lib.call("kfa_adam_bc", _lib.ptr(self._t), _lib.ptr(self._bc), self.b1, self.b2, seed, _lib.stream())
         self.step_count += 1
 
 
@@ -306,10 +318,8 @@ class FusedAdam(_AdamMoments):
         w, wb, gr = s.w[a:b], (s.wb[a:b] if s.wb is not None else None), s.grad[a:b]
         m, v = self.m[si][a:b], self.v[si][a:b]
         wd = self._wd(s)
-        if self._cpu(s):
-            d = gr.float() * grad_scale
-            if self._clip is not None:
-                d = d * self._clip[1]
+        if not self._gpu:
+            d = self._cpu_grad(gr, grad_scale)
             m.mul_(self.b1).add_(d, alpha=1 - self.b1)
             v.mul_(self.b2).addcmul_(d, d, value=1 - self.b2)
             denom = (v.sqrt() / math.sqrt(bc2)).add_(self.eps)
@@ -318,24 +328,46 @@ class FusedAdam(_AdamMoments):
                 wb.copy_(w)
             return
         if self._clip is not None:
-            _lib.call("kfa_adam_step_clip", _lib.ptr(w), _lib.ptr(wb), _lib.ptr(gr), int(gr.dtype == torch.bfloat16),
-                      _lib.ptr(m), _lib.ptr(v), b - a, lr, self.b1, self.b2, self.eps, wd, grad_scale,
-                      _lib.ptr(self._bc), self._dcoef(), _lib.stream())
+            _lib.call("kfa_adam_step_clip", _lib.ptr(w), _lib.ptr(wb), *_garg(gr), _lib.ptr(m), _lib.ptr(v), b - a, lr,
+                      self.b1, self.b2, self.eps, wd, grad_scale, _lib.ptr(self._bc), self._dcoef, _lib.stream())
             return
-        _lib.call("kfa_adam_step", _lib.ptr(w), _lib.ptr(wb), _lib.ptr(gr), int(gr.dtype == torch.bfloat16),
-                  _lib.ptr(m), _lib.ptr(v), b - a, lr, self.b1, self.b2, self.eps, wd, bc1, bc2, grad_scale,
-                  _lib.ptr(self._bc), _lib.stream())
+        _lib.call("kfa_adam_step", _lib.ptr(w), _lib.ptr(wb), *_garg(gr), _lib.ptr(m), _lib.ptr(v), b - a, lr,
+                  self.b1, self.b2, self.eps, wd, bc1, bc2, grad_scale, _lib.ptr(self._bc), _lib.stream())
 
-    @torch.no_grad()
-    def step(self, grad_scale: float = 1.0, lr: Optional[float] = None) -> None:
-        self.begin_step()
-        if self._clip is not None:
-            self._clip_scalar(grad_scale)
-        for si, s in enumerate(self.spaces):
-            self.update(si, 0, s.numel, grad_scale, lr)
+class _TrustRatios:
+    """What LAMB and LARS share, mixed in ahead of their state class: per adapting space
+    (``adapt_groups``) ``_ratio`` holds an entry per tensor and, on the GPU, ``_part`` ``PARTS`` partial
+    sums per chunk; both are ``None`` for a space that does not adapt.  The ratios are norms of whole
+    tensors, so a space without ``segments`` is refused."""
+
+    PARTS = 1
+
+    def __init__(self, spaces, *args, adapt_groups=None, **kw):
+        name = type(self).__name__
+        for s in _as_spaces(spaces):
+            if s.segments is None:
+                raise ValueError(f"{name}: optimizer space {s.name!r} has no per-tensor segments "
+                                 f"(a sharded layout); {name[len('Fused'):]} needs whole tensors for its trust ratios")
+        super().__init__(spaces, *args, **kw)
+        self.adapt_groups = set(adapt_groups) if adapt_groups is not None else set(self.decay_groups)
+        self._ratio = [torch.ones(len(s.segments), dtype=torch.float32, device=s.device) if self._adapts(s) else None
+                       for s in self.spaces]
+        if self._gpu:
+            self._part = [torch.zeros(self.PARTS * t.nchunks, dtype=torch.float32, device=s.device)
+                          if self._adapts(s) else None for s, t in zip(self.spaces, self._tables())]
+
+    def _adapts(self, s: OptSpace) -> bool:
+        return s.name in self.adapt_groups or not s.name
+
+    @property
+    def trust_ratios(self) -> List[Optional[torch.Tensor]]:
+        """Per space, the trust ratios of the last step: one tensor on the space's
+        device with an entry per tensor, or ``None`` for a space that does not adapt.
+        For logging: the step writes them, nothing may write them from outside."""
+        return list(self._ratio)
 
 
-class FusedLAMB(_AdamMoments):
+class FusedLAMB(_TrustRatios, _AdamMoments):
     """LAMB (You et al., 2020): Adam's moments, and per tensor ``t`` of a space
 
         u = (m / bc1) / (sqrt(v / bc2) + eps) + wd * w
@@ -350,22 +382,11 @@ class FusedLAMB(_AdamMoments):
     not elementwise: there is no ranged ``update``, and every space needs its
     tensors' ``segments`` (the compact parameter-server shards have none)."""
 
+    PARTS = 2  # the kernels' layout: part[2c], part[2c + 1] = the sums of w^2, u^2 of chunk c
+
     def __init__(self, spaces, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, decay_groups=None,
                  adapt_groups=None, max_grad_norm=None):
-        for s in _as_spaces(spaces):
-            if s.segments is None:
-                raise ValueError(f"FusedLAMB: optimizer space {s.name!r} has no per-tensor segments "
-                                 "(a sharded layout); LAMB needs whole tensors for its trust ratios")
-        super().__init__(spaces, lr, betas, eps, weight_decay, decay_groups, max_grad_norm)
-        self.adapt_groups = set(adapt_groups) if adapt_groups is not None else set(self.decay_groups)
-        self._part, self._ratio = [], []
-        for s, t in zip(self.spaces, self._tables() if self._t is not None else []):
-            adapt = self._adapts(s)
-            self._part.append(torch.zeros(2 * t.nchunks, dtype=torch.float32, device=s.device) if adapt else None)
-            self._ratio.append(torch.ones(t.ntens, dtype=torch.float32, device=s.device) if adapt else None)
-
-    def _adapts(self, s: OptSpace) -> bool:
-        return s.name in self.adapt_groups or not s.name
+        super().__init__(spaces, lr, betas, eps, weight_decay, decay_groups, max_grad_norm, adapt_groups=adapt_groups)
 
     @torch.no_grad()
     def step(self, grad_scale: float = 1.0, lr: Optional[float] = None) -> None:
@@ -373,47 +394,45 @@ class FusedLAMB(_AdamMoments):
         lr = self.lr if lr is None else lr
         if self._clip is not None:
             self._clip_scalar(grad_scale)
-        for si, s in enumerate(self.spaces):
-            if self._cpu(s):
+        if not self._gpu:
+            for si in range(len(self.spaces)):
                 self._cpu_step(si, grad_scale, lr)
-                continue
-            t, g = self._tables()[si], s.grad
-            part, ratio, wd = self._part[si], self._ratio[si], self._wd(s)
-            _lib.call("kfa_lamb_stage1", _lib.ptr(s.w), _lib.ptr(g), int(g.dtype == torch.bfloat16),
-                      _lib.ptr(self.m[si]), _lib.ptr(self.v[si]), _lib.ptr(t.chunks), t.nchunks, _lib.ptr(part),
-                      self.b1, self.b2, self.eps, wd, grad_scale, _lib.ptr(self._bc), self._dcoef(), _lib.stream())
+            return
+        stream, bc, dcoef = _lib.stream(), _lib.ptr(self._bc), self._dcoef
+        for si, (s, t) in enumerate(zip(self.spaces, self._tables())):
+            w, m, v, chunks = _lib.ptr(s.w), _lib.ptr(self.m[si]), _lib.ptr(self.v[si]), _lib.ptr(t.chunks)
+            part, ratio, wd = _lib.ptr(self._part[si]), _lib.ptr(self._ratio[si]), self._wd(s)
+            _lib.call("kfa_lamb_stage1", w, *_garg(s.grad), m, v, chunks, t.nchunks, part, self.b1, self.b2, self.eps,
+                      wd, grad_scale, bc, dcoef, stream)
             if ratio is not None:
-                _lib.call("kfa_lamb_ratio", _lib.ptr(part), _lib.ptr(t.tens), t.ntens, _lib.ptr(ratio),
-                          _lib.stream())
-            _lib.call("kfa_lamb_stage2", _lib.ptr(s.w), _lib.ptr(s.wb), _lib.ptr(self.m[si]), _lib.ptr(self.v[si]),
-                      _lib.ptr(t.chunks), t.nchunks, _lib.ptr(ratio), lr, self.eps, wd, _lib.ptr(self._bc),
-                      _lib.stream())
+                _lib.call("kfa_lamb_ratio", part, _lib.ptr(t.tens), t.ntens, ratio, stream)
+            _lib.call("kfa_lamb_stage2", w, _lib.ptr(s.wb), m, v, chunks, t.nchunks, ratio, lr, self.eps, wd, bc,
+                      stream)
 
     def _cpu_step(self, si: int, grad_scale: float, lr: float) -> None:
         s = self.spaces[si]
         bc1 = 1.0 - self.b1 ** self.step_count
         bc2 = 1.0 - self.b2 ** self.step_count
-        wd, adapt = self._wd(s), self._adapts(s)
+        wd, ratio = self._wd(s), self._ratio[si]
         gr = s.grad
-        for a, n in s.segments:
+        for k, (a, n) in enumerate(s.segments):
             w, m, v = s.w[a:a + n], self.m[si][a:a + n], self.v[si][a:a + n]
-            d = gr[a:a + n].float() * grad_scale
-            if self._clip is not None:
-                d = d * self._clip[1]
+            d = self._cpu_grad(gr[a:a + n], grad_scale)
             m.mul_(self.b1).add_(d, alpha=1 - self.b1)
             v.mul_(self.b2).addcmul_(d, d, value=1 - self.b2)
             u = (m / bc1) / ((v / bc2).sqrt() + self.eps) + wd * w
             r = 1.0
-            if adapt:
+            if ratio is not None:
                 wn, un = float(w.norm()), float(u.norm())
                 if wn > 0 and un > 0:
                     r = wn / un
+                ratio[k] = r
             w.add_(u, alpha=-lr * r)
         if s.wb is not None:
             s.wb.copy_(s.w)
 
 
-class FusedLARS(_FusedBase):
+class FusedLARS(_TrustRatios, _FusedBase):
     """LARS (You, Gitman, Ginsburg, 2017): momentum SGD whose update of tensor ``t`` of
     a space is scaled by a layer-wise rate.  With g~ = g * grad_scale * clip
 
@@ -444,73 +463,46 @@ class FusedLARS(_FusedBase):
 
     def __init__(self, spaces, lr=0.1, momentum=0.9, weight_decay=5e-5, trust=0.001, eps=1e-8, nesterov=False,
                  decay_groups=None, adapt_groups=None, max_grad_norm=None):
-        for s in _as_spaces(spaces):
-            if s.segments is None:
-                raise ValueError(f"FusedLARS: optimizer space {s.name!r} has no per-tensor segments "
-                                 "(a sharded layout); LARS needs whole tensors for its trust ratios")
-        super().__init__(spaces, lr, weight_decay, decay_groups, max_grad_norm)
+        super().__init__(spaces, lr, weight_decay, decay_groups, max_grad_norm, g2_partials=True,
+                         adapt_groups=adapt_groups)
         self.momentum = momentum
         self.trust = trust
         self.eps = eps
         self.nesterov = nesterov
-        self.adapt_groups = set(adapt_groups) if adapt_groups is not None else set(self.decay_groups)
         self.mom = [torch.zeros(s.numel, dtype=torch.float32, device=s.device) for s in self.spaces]
-        self._ratio = [torch.ones(len(s.segments), dtype=torch.float32, device=s.device) if self._adapts(s) else None
-                       for s in self.spaces]
-        self._part = []  # GPU: per chunk of an adapting space, the sum of w^2
-        if self.spaces and self.spaces[0].device.type == "cuda":
-            self._part = [torch.zeros(t.nchunks, dtype=torch.float32, device=s.device) if self._adapts(s) else None
-                          for s, t in zip(self.spaces, self._tables())]
-            if self._clip is None:  # the g^2 partials, in the layout _clip_scalar gives them when clipping
-                self._gpart = torch.zeros(sum(t.nchunks for t in self._tables()), dtype=torch.float32,
-                                          device=self.spaces[0].device)
 
-    def _adapts(self, s: OptSpace) -> bool:
-        return s.name in self.adapt_groups or not s.name
-
-    @property
-    def trust_ratios(self) -> List[Optional[torch.Tensor]]:
-        """Per space, the rates ``lambda_t`` of the last step: one tensor on the space's
-        device with an entry per tensor, or ``None`` for a space that does not adapt.
-        For logging: the step writes them, nothing may write them from outside."""
-        return list(self._ratio)
+    def _g2_partials(self, si: int, stream: int) -> None:
+        """An adapting space's norms pass: its w^2 partials into ``_part``, and its g^2 partials
+        where the clip norm takes them."""
+        if self._ratio[si] is None:
+            return _FusedBase._g2_partials(self, si, stream)
+        s, t = self.spaces[si], self._tabs[si]
+        _lib.call("kfa_lars_norms", _lib.ptr(s.w), *_garg(s.grad), _lib.ptr(t.chunks), t.nchunks,
+                  _lib.ptr(self._part[si]), self._gaddr[si], stream)
 
     @torch.no_grad()
     def step(self, grad_scale: float = 1.0, lr: Optional[float] = None) -> None:
         self.step_count += 1
         lr = self.lr if lr is None else lr
-        if not self.spaces:
-            return
-        if self._cpu(self.spaces[0]):
-            if self._clip is not None:
-                self._clip_scalar(grad_scale)
+        stream, dcoef = _lib.stream() if self._gpu else None, self._dcoef
+        if self._clip is not None:  # GPU: every space's g^2 partials, the adapting ones' from their norms pass
+            self._clip_scalar(grad_scale, stream)
+        if not self._gpu:
             for si in range(len(self.spaces)):
                 self._cpu_step(si, grad_scale, lr)
             return
-        tabs, stream = self._tables(), _lib.stream()
-        off, gparts = 0, []
-        for si, (s, t) in enumerate(zip(self.spaces, tabs)):
-            g = s.grad
-            gpart = self._gpart.data_ptr() + 4 * off
-            if self._ratio[si] is not None:
-                _lib.call("kfa_lars_norms", _lib.ptr(s.w), _lib.ptr(g), int(g.dtype == torch.bfloat16),
-                          _lib.ptr(t.chunks), t.nchunks, _lib.ptr(self._part[si]), gpart, stream)
-            elif self._clip is not None:  # its share of the global norm
-                _lib.call("kfa_chunk_sumsq", _lib.ptr(g), int(g.dtype == torch.bfloat16), _lib.ptr(t.chunks),
-                          t.nchunks, gpart, stream)
-            gparts.append(gpart)
-            off += t.nchunks
-        if self._clip is not None:
-            _lib.call("kfa_clip_finish", _lib.ptr(self._gpart), off, grad_scale, self.max_grad_norm,
-                      _lib.ptr(self._clip), stream)
-        for si, (s, t) in enumerate(zip(self.spaces, tabs)):
-            g, ratio, wd = s.grad, self._ratio[si], self._wd(s)
+        if self._clip is None:
+            for si, ratio in enumerate(self._ratio):
+                if ratio is not None:
+                    self._g2_partials(si, stream)
+        for si, (s, t) in enumerate(zip(self.spaces, self._tabs)):
+            ratio, wd = _lib.ptr(self._ratio[si]), self._wd(s)
             if ratio is not None:
-                _lib.call("kfa_lars_ratio", _lib.ptr(self._part[si]), gparts[si], _lib.ptr(t.tens), t.ntens,
-                          _lib.ptr(ratio), grad_scale, self._dcoef(), self.trust, wd, self.eps, stream)
-            _lib.call("kfa_lars_apply", _lib.ptr(s.w), _lib.ptr(s.wb), _lib.ptr(g), int(g.dtype == torch.bfloat16),
-                      _lib.ptr(self.mom[si]), _lib.ptr(t.chunks), t.nchunks, _lib.ptr(ratio), lr, self.momentum, wd,
-                      int(self.nesterov), grad_scale, self._dcoef(), stream)
+                _lib.call("kfa_lars_ratio", _lib.ptr(self._part[si]), self._gaddr[si], _lib.ptr(t.tens), t.ntens, ratio,
+                          grad_scale, dcoef, self.trust, wd, self.eps, stream)
+            _lib.call("kfa_lars_apply", _lib.ptr(s.w), _lib.ptr(s.wb), *_garg(s.grad), _lib.ptr(self.mom[si]),
+                      _lib.ptr(t.chunks), t.nchunks, ratio, lr, self.momentum, wd, int(self.nesterov), grad_scale,
+                      dcoef, stream)
 
     def _cpu_step(self, si: int, grad_scale: float, lr: float) -> None:
         s = self.spaces[si]
@@ -518,9 +510,7 @@ class FusedLARS(_FusedBase):
         gr = s.grad
         for k, (a, n) in enumerate(s.segments):
             w, mom = s.w[a:a + n], self.mom[si][a:a + n]
-            d = gr[a:a + n].float() * grad_scale
-            if self._clip is not None:
-                d = d * self._clip[1]
+            d = self._cpu_grad(gr[a:a + n], grad_scale)
             lam = 1.0
             if ratio is not None:
                 wn, gn = float(w.double().norm()), float(d.double().norm())  # fp32 sums drift at 1e6 elements

@@ -108,18 +108,18 @@ class Engine:
                  grad_reduce_dtype: Optional[torch.dtype] = torch.float32, comm=None,
                  opt_overlap: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  nesterov: bool = False, trust_coefficient: float = 0.001):
-        from ..ops.optim import FusedAdam, FusedLAMB, FusedLARS, FusedSGD
+        from ..ops.optim import CLIPS, FusedAdam, FusedLAMB, FusedLARS, FusedSGD, needs_whole_grad
         from ..parallel.ddp import GradSync, broadcast_params
 
         self.info = dist_info or DistInfo()
         # LAMB's / LARS's per-tensor norms and the clip's global norm are taken over whole gradients
-        whole_grad = optimizer in ("lamb", "lars") or max_grad_norm is not None
+        whole_grad = needs_whole_grad(optimizer, max_grad_norm)
         if whole_grad and ps > 0 and self.info.world > 1:  # before any collective: every rank raises
             raise ValueError("optimizer='lamb' / 'lars' / max_grad_norm need the whole gradient on every rank "
                              "(data-parallel all-reduce, ps=0): in the sharded parameter-server layouts a rank holds "
                              "only its shard, and norms across shards are not built")
-        if optimizer == "sgd" and max_grad_norm is not None:
-            raise ValueError("max_grad_norm: gradient clipping is not built for optimizer='sgd' "
+        if max_grad_norm is not None and optimizer not in CLIPS:
+            raise ValueError(f"max_grad_norm: gradient clipping is not built for optimizer={optimizer!r} "
                              "(use adam, lamb or lars)")
         if self.info.world > 1:  # per-shape tuner decisions are broadcast from rank 0 (ops/conv._agree)
             from ..ops import conv as _conv

@@ -212,10 +212,12 @@ def _check_whole_gradient(spec: ClusterSpec, args, async_mode: bool) -> None:
     """LAMB's and LARS's per-tensor norms and the clip's global norm need every worker to hold the
     whole reduced gradient: the all-reduce layout (or one replica).  Raises ValueError for
     the async PS mode, whose PS tasks keep Adam / SGD, and for the sharded collective layouts."""
-    if args.optimizer not in ("lamb", "lars") and args.max_grad_norm is None:
+    from ..ops.optim import CLIPS, needs_whole_grad
+    if not needs_whole_grad(args.optimizer, args.max_grad_norm):
         return
-    if args.optimizer == "sgd":
-        raise ValueError("--max_grad_norm: gradient clipping is not built for --optimizer sgd (use adam, lamb or lars)")
+    if args.optimizer not in CLIPS:
+        raise ValueError(f"--max_grad_norm: gradient clipping is not built for --optimizer {args.optimizer} "
+                         "(use adam, lamb or lars)")
     if async_mode:
         raise ValueError("--optimizer lamb / lars / --max_grad_norm are not available in the async parameter-server "
                          "mode: its PS tasks apply Adam or SGD per pushed gradient (parallel/async_ps.py); "

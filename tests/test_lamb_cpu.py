@@ -2,36 +2,18 @@
 reference of the formulas, across two gloo ranks, through a checkpoint round
 trip, and the configurations that are refused."""
 import os
-import socket
 import sys
 
 import pytest
 import torch
 import torch.multiprocessing as mp
 
+import _optim_ref as R
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SHAPES_W = [(5,), (768,), (64, 33), (40, 41)]
 SHAPES_B = [(11,), (768,)]
-
-
-def _ref_clip(grads, gscale, max_norm):
-    """(pre-clip norm, coefficient) of torch.nn.utils.clip_grad_norm_ in fp64; coefficient 1 without max_norm."""
-    norm = gscale * torch.sqrt(sum(g.double().pow(2).sum() for g in grads))
-    if max_norm is None:
-        return norm, 1.0
-    return norm, min(1.0, float(max_norm / (norm + 1e-6)))
-
-
-def _ref_lamb_step(w, m, v, g, t, *, lr, b1, b2, eps, wd, adapt, gs):
-    """One LAMB step of one tensor in fp64, in place; gs = gscale * clip."""
-    g = g.double() * gs
-    m.mul_(b1).add_((1 - b1) * g)
-    v.mul_(b2).add_((1 - b2) * g * g)
-    u = (m / (1 - b1 ** t)) / ((v / (1 - b2 ** t)).sqrt() + eps) + wd * w
-    wn, un = float(w.norm()), float(u.norm())
-    r = wn / un if (adapt and wn > 0 and un > 0) else 1.0
-    w.sub_(lr * r * u)
 
 
 def _ref_adam_step(w, m, v, g, t, *, lr, b1, b2, eps, wd, gs):
@@ -41,19 +23,8 @@ def _ref_adam_step(w, m, v, g, t, *, lr, b1, b2, eps, wd, gs):
     w.mul_(1 - lr * wd).sub_(lr * (m / (1 - b1 ** t)) / ((v / (1 - b2 ** t)).sqrt() + eps))
 
 
-def _groups(pad_to=64):
-    from kubeflow_controller_amd.parallel.flat import FlatGroup
-    torch.manual_seed(7)
-    pw = [torch.nn.Parameter(torch.randn(*s)) for s in SHAPES_W]
-    pb = [torch.nn.Parameter(torch.randn(*s)) for s in SHAPES_B]
-    return (FlatGroup(pw, pad_to=pad_to, name="weights"), FlatGroup(pb, pad_to=pad_to, name="norms_biases"))
-
-
-def _pad_mask(g):
-    mask = torch.ones(g.numel, dtype=torch.bool)
-    for o, p in zip(g.offsets, g.params):
-        mask[o:o + p.numel()] = False
-    return mask
+def _groups():
+    return R.cpu_groups(SHAPES_W, SHAPES_B)
 
 
 @pytest.mark.parametrize("max_norm", [None, 0.5])
@@ -69,30 +40,19 @@ def test_cpu_lamb_matches_fp64_reference(max_norm):
     gen = torch.Generator().manual_seed(11)
     for t in range(1, 5):
         grads = [[torch.randn(p.shape, generator=gen) for p in g.params] for g in (gw, gb)]
-        for g, gs in zip((gw, gb), grads):
-            g.zero_grad()
-            for p, x in zip(g.params, gs):
-                p.grad.copy_(x)
+        R.set_grads((gw, gb), grads)
         opt.step(grad_scale=0.5)
-        norm, coef = _ref_clip([x for gs in grads for x in gs], 0.5, max_norm)
+        norm, coef = R.ref_clip([x for gs in grads for x in gs], 0.5, max_norm)
         for gi in range(2):
             for k in range(len(ref[gi])):
-                _ref_lamb_step(ref[gi][k], rm[gi][k], rv[gi][k], grads[gi][k], t,
-                               **{**hp, "wd": hp["wd"] if gi == 0 else 0.0}, adapt=gi == 0, gs=0.5 * coef)
+                R.ref_lamb_step(ref[gi][k], rm[gi][k], rv[gi][k], grads[gi][k], t,
+                                **{**hp, "wd": hp["wd"] if gi == 0 else 0.0}, adapt=gi == 0, gs=0.5 * coef)
         if max_norm is not None:
             assert coef < 1.0  # the clip is active
             torch.testing.assert_close(opt.last_grad_norm.double(), norm, rtol=1e-5, atol=0)
     assert opt.last_grad_norm is None or opt.last_grad_norm.dim() == 0
-    for gi, g in enumerate((gw, gb)):
-        for k, (o, p) in enumerate(zip(g.offsets, g.params)):
-            n = p.numel()
-            torch.testing.assert_close(p.detach().double(), ref[gi][k], atol=1e-4, rtol=1e-4)
-            torch.testing.assert_close(opt.m[gi][o:o + n].double(), rm[gi][k].flatten(), atol=1e-4, rtol=1e-4)
-            torch.testing.assert_close(opt.v[gi][o:o + n].double(), rv[gi][k].flatten(), atol=1e-4, rtol=1e-4)
-        pad = _pad_mask(g)
-        assert pad.any()
-        for buf in (g.fp32, opt.m[gi], opt.v[gi]):
-            assert torch.equal(buf[pad], torch.zeros(int(pad.sum())))
+    R.check_against((gw, gb), ([gw.fp32, gb.fp32], opt.m, opt.v),
+                    [[[x.flatten() for x in r] for r in rs] for rs in (ref, rm, rv)])
 
 
 def test_cpu_clipped_adam_matches_fp64_reference():
@@ -106,12 +66,9 @@ def test_cpu_clipped_adam_matches_fp64_reference():
     gen = torch.Generator().manual_seed(12)
     for t in range(1, 5):
         grads = [[torch.randn(p.shape, generator=gen) for p in g.params] for g in (gw, gb)]
-        for g, gs in zip((gw, gb), grads):
-            g.zero_grad()
-            for p, x in zip(g.params, gs):
-                p.grad.copy_(x)
+        R.set_grads((gw, gb), grads)
         opt.step()
-        norm, coef = _ref_clip([x for gs in grads for x in gs], 1.0, 1.0)
+        norm, coef = R.ref_clip([x for gs in grads for x in gs], 1.0, 1.0)
         assert coef < 0.1
         torch.testing.assert_close(opt.last_grad_norm.double(), norm, rtol=1e-5, atol=0)
         for gi in range(2):
@@ -124,36 +81,6 @@ def test_cpu_clipped_adam_matches_fp64_reference():
 
 
 # ------------------------------------------------------------------ two gloo ranks == one process
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _model():
-    torch.manual_seed(0)
-    return torch.nn.Sequential(torch.nn.Linear(12, 32), torch.nn.ReLU(), torch.nn.Linear(32, 5))
-
-
-def _data():
-    g = torch.Generator().manual_seed(1)
-    return torch.randn(16, 12, generator=g), torch.randint(0, 5, (16,), generator=g)
-
-
-def _train(model, opt, sync, x, y, steps):
-    import torch.nn.functional as F
-    norms = []
-    for _ in range(steps):
-        for g in sync.groups:
-            g.zero_grad()
-        F.cross_entropy(model(x), y).backward()
-        opt.step(grad_scale=sync.finish())
-        norms.append(float(opt.last_grad_norm))
-    return norms
-
-
 # the clip is active on every step: the gradient norm of this model stays above 0.3
 DP_CLIP = 0.05
 
@@ -166,14 +93,14 @@ def _dp_worker(rank, world, port, out):
     from kubeflow_controller_amd.parallel.flat import split_params
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    model = _model()
+    model = R.model()
     groups = split_params(model, None, pad_to=8 * world)
     broadcast_params(groups)
     sync = GradSync(groups, bucket_mb=0.0005)  # several buckets
     opt = FusedLAMB(sync.spaces(), lr=0.01, max_grad_norm=DP_CLIP)
-    x, y = _data()
+    x, y = R.data()
     n = x.shape[0] // world
-    norms = _train(model, opt, sync, x[rank * n:(rank + 1) * n], y[rank * n:(rank + 1) * n], 5)
+    norms = R.train(model, opt, sync, x[rank * n:(rank + 1) * n], y[rank * n:(rank + 1) * n], 5)
     torch.save({"sd": {k: v.clone() for k, v in model.state_dict().items()}, "norms": norms,
                 "buckets": len(sync.buckets)}, f"{out}.{rank}")
     dist.barrier()
@@ -185,11 +112,11 @@ def test_dp_lamb_clip_matches_single_process(tmp_path):
     from kubeflow_controller_amd.parallel.ddp import GradSync
     from kubeflow_controller_amd.parallel.flat import split_params
     out = str(tmp_path / "res")
-    mp.start_processes(_dp_worker, args=(2, _free_port(), out), nprocs=2, join=True, start_method="spawn")
-    model = _model()
+    mp.start_processes(_dp_worker, args=(2, R.free_port(), out), nprocs=2, join=True, start_method="spawn")
+    model = R.model()
     sync = GradSync(split_params(model, None))
     opt = FusedLAMB(sync.spaces(), lr=0.01, max_grad_norm=DP_CLIP)
-    norms = _train(model, opt, sync, *_data(), 5)
+    norms = R.train(model, opt, sync, *R.data(), 5)
     assert min(norms) > 2 * DP_CLIP, norms
     for r in range(2):
         got = torch.load(f"{out}.{r}", weights_only=True)
@@ -204,13 +131,13 @@ def _engine(**kw):
     from kubeflow_controller_amd.trainer.engine import DistInfo, Engine
     import torch.nn.functional as F
     kw.setdefault("optimizer", "lamb")
-    return Engine(_model(), lambda m, x, y: F.cross_entropy(m(x), y), lr=0.01, weight_decay=0.01, compute_dtype=None,
+    return Engine(R.model(), lambda m, x, y: F.cross_entropy(m(x), y), lr=0.01, weight_decay=0.01, compute_dtype=None,
                   channels_last=False, dist_info=kw.pop("dist_info", DistInfo()), **kw)
 
 
 def test_lamb_engine_checkpoint_round_trip_continues_bit_identically(tmp_path):
     from kubeflow_controller_amd.ops.optim import FusedLAMB
-    x, y = _data()
+    x, y = R.data()
     a = _engine(max_grad_norm=DP_CLIP)
     assert isinstance(a.opt, FusedLAMB) and a.opt.max_grad_norm == DP_CLIP and not a.opt_overlap
     for _ in range(3):

@@ -8,6 +8,8 @@ import copy
 import pytest
 import torch
 
+import _optim_ref as R
+
 pytestmark = pytest.mark.gpu
 
 # 5: under one vector; 64x33: numel % 8 != 0; 300x300: several chunks and a ragged last one
@@ -17,58 +19,21 @@ SHAPES_B = [(11,), (768,)]
 HP = dict(lr=1e-2, b1=0.9, b2=0.999, eps=1e-6, wd=0.01)
 
 
-def _dev():
-    return torch.device("cuda")
-
-
-def _ref_clip(grads, gscale, max_norm):
-    norm = gscale * torch.sqrt(sum(g.double().pow(2).sum() for g in grads))
-    if max_norm is None:
-        return norm, 1.0
-    return norm, min(1.0, float(max_norm / (norm + 1e-6)))
-
-
-def _ref_lamb_step(w, m, v, g, t, *, lr, b1, b2, eps, wd, adapt, gs):
-    """One LAMB step of one tensor in fp64, in place; gs = gscale * clip."""
-    g = g.double() * gs
-    m.mul_(b1).add_((1 - b1) * g)
-    v.mul_(b2).add_((1 - b2) * g * g)
-    u = (m / (1 - b1 ** t)) / ((v / (1 - b2 ** t)).sqrt() + eps) + wd * w
-    wn, un = float(w.norm()), float(u.norm())
-    r = wn / un if (adapt and wn > 0 and un > 0) else 1.0
-    w.sub_(lr * r * u)
-
-
 def _groups(wdtype, seed=7, shapes_w=SHAPES_W, init=None):
     """Two flat groups with a group tail (pad_to=64): "weights" in ``wdtype`` (bf16: with an
     fp32 master and a bf16 compute copy, bf16 gradients) and fp32 1-D "norms_biases"."""
-    from kubeflow_controller_amd.parallel.flat import FlatGroup
     torch.manual_seed(seed)
-    pw = [torch.nn.Parameter(torch.randn(*s, device=_dev()).to(wdtype)) for s in shapes_w]
-    pb = [torch.nn.Parameter(torch.randn(*s, device=_dev())) for s in SHAPES_B]
+    pw = [torch.nn.Parameter(torch.randn(*s, device=R.dev()).to(wdtype)) for s in shapes_w]
+    pb = [torch.nn.Parameter(torch.randn(*s, device=R.dev())) for s in SHAPES_B]
     if init is not None:
         init(pw)
-    return FlatGroup(pw, pad_to=64, name="weights"), FlatGroup(pb, pad_to=64, name="norms_biases")
+    return R.flat_pair(pw, pb)
 
 
 def _rand_grads(groups, gen, scale=1.0):
     """Per group, per tensor: random gradients already rounded to the group's gradient dtype."""
-    return [[(torch.randn(p.shape, generator=gen, device=_dev()) * scale).to(g.grad.dtype) for p in g.params]
+    return [[(torch.randn(p.shape, generator=gen, device=R.dev()) * scale).to(g.grad.dtype) for p in g.params]
             for g in groups]
-
-
-def _set_grads(groups, grads):
-    for g, gs in zip(groups, grads):
-        g.zero_grad()
-        for p, x in zip(g.params, gs):
-            p.grad.copy_(x)
-
-
-def _pad_mask(g):
-    mask = torch.ones(g.numel, dtype=torch.bool, device=g.device)
-    for o, p in zip(g.offsets, g.params):
-        mask[o:o + p.numel()] = False
-    return mask
 
 
 def _run_vs_reference(groups, opt, grads_per_step, *, wd, gscale=1.0, max_norm=None):
@@ -78,28 +43,16 @@ def _run_vs_reference(groups, opt, grads_per_step, *, wd, gscale=1.0, max_norm=N
     rm = [[torch.zeros_like(x) for x in r] for r in ref]
     rv = [[torch.zeros_like(x) for x in r] for r in ref]
     for t, grads in enumerate(grads_per_step, start=1):
-        _set_grads(groups, grads)
+        R.set_grads(groups, grads)
         opt.step(grad_scale=gscale)
-        _, coef = _ref_clip([x for gs in grads for x in gs], gscale, max_norm)
+        _, coef = R.ref_clip([x for gs in grads for x in gs], gscale, max_norm)
         for gi in range(len(groups)):
             for k in range(len(ref[gi])):
-                _ref_lamb_step(ref[gi][k], rm[gi][k], rv[gi][k], grads[gi][k].flatten(), t, lr=HP["lr"], b1=HP["b1"],
-                               b2=HP["b2"], eps=HP["eps"], wd=wd if gi == 0 else 0.0, adapt=gi == 0,
-                               gs=gscale * coef)
+                R.ref_lamb_step(ref[gi][k], rm[gi][k], rv[gi][k], grads[gi][k].flatten(), t, lr=HP["lr"], b1=HP["b1"],
+                                b2=HP["b2"], eps=HP["eps"], wd=wd if gi == 0 else 0.0, adapt=gi == 0,
+                                gs=gscale * coef)
     torch.cuda.synchronize()
-    for gi, g in enumerate(groups):
-        for k, (o, p) in enumerate(zip(g.offsets, g.params)):
-            n = p.numel()
-            for got, want in ((g.fp32[o:o + n], ref[gi][k]), (opt.m[gi][o:o + n], rm[gi][k]),
-                              (opt.v[gi][o:o + n], rv[gi][k])):
-                assert torch.isfinite(got).all()
-                torch.testing.assert_close(got.double(), want, atol=1e-4, rtol=1e-4)
-            if g.master is not None:
-                torch.testing.assert_close(p.detach().flatten().double(), ref[gi][k], atol=2e-2, rtol=1e-2)
-        pad = _pad_mask(g)
-        assert pad.any()
-        for buf in (g.fp32, opt.m[gi], opt.v[gi], g.data.float()):
-            assert torch.count_nonzero(buf[pad]) == 0, "padding must stay exactly 0"
+    R.check_against(groups, ([g.fp32 for g in groups], opt.m, opt.v), (ref, rm, rv))
 
 
 @pytest.mark.parametrize("wdtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
@@ -112,11 +65,11 @@ def test_lamb_matches_fp64_reference(wdtype, max_norm):
     assert groups[0].grad.dtype == wdtype
     opt = FusedLAMB(groups, lr=HP["lr"], betas=(HP["b1"], HP["b2"]), eps=HP["eps"], weight_decay=HP["wd"],
                     max_grad_norm=max_norm)
-    gen = torch.Generator(device=_dev()).manual_seed(5)
+    gen = torch.Generator(device=R.dev()).manual_seed(5)
     steps = [_rand_grads(groups, gen) for _ in range(4)]
     _run_vs_reference(groups, opt, steps, wd=HP["wd"], gscale=0.5, max_norm=max_norm)
     if max_norm is not None:
-        norm, coef = _ref_clip([x for gs in steps[-1] for x in gs], 0.5, max_norm)
+        norm, coef = R.ref_clip([x for gs in steps[-1] for x in gs], 0.5, max_norm)
         assert coef < 0.1  # the clip was active
         torch.testing.assert_close(opt.last_grad_norm.double(), norm, rtol=1e-5, atol=0)
 
@@ -131,7 +84,7 @@ def test_lamb_trust_ratio_edge_cases():
     shapes = [(40, 9), (129,), (64, 33)]
     groups = _groups(torch.float32, seed=9, shapes_w=shapes, init=init)
     opt = FusedLAMB(groups, lr=HP["lr"], betas=(HP["b1"], HP["b2"]), eps=HP["eps"], weight_decay=0.0)
-    gen = torch.Generator(device=_dev()).manual_seed(6)
+    gen = torch.Generator(device=R.dev()).manual_seed(6)
     steps = [_rand_grads(groups, gen) for _ in range(3)]
     for grads in steps:
         grads[0][1].zero_()  # tensor 1 of "weights": no gradient ever, so m = v = u = 0
@@ -147,7 +100,7 @@ def _state(groups, opt):
 
 def test_lamb_step_is_bit_repeatable():
     from kubeflow_controller_amd.ops.optim import FusedLAMB
-    gen = torch.Generator(device=_dev()).manual_seed(8)
+    gen = torch.Generator(device=R.dev()).manual_seed(8)
     out = []
     steps = None
     for _ in range(2):
@@ -156,7 +109,7 @@ def test_lamb_step_is_bit_repeatable():
         if steps is None:
             steps = [_rand_grads(groups, gen) for _ in range(3)]
         for grads in steps:
-            _set_grads(groups, grads)
+            R.set_grads(groups, grads)
             opt.step()
         torch.cuda.synchronize()
         assert float(opt.last_grad_norm) > 10.0  # clipping active
@@ -172,10 +125,10 @@ def test_adam_clipping_matches_torch():
     opt = FusedAdam(groups, lr=1e-2, weight_decay=0.1, max_grad_norm=1.0)
     topt = torch.optim.AdamW([{"params": refs[0], "weight_decay": 0.1}, {"params": refs[1], "weight_decay": 0.0}],
                              lr=1e-2)
-    gen = torch.Generator(device=_dev()).manual_seed(4)
+    gen = torch.Generator(device=R.dev()).manual_seed(4)
     for _ in range(4):
         grads = _rand_grads(groups, gen)
-        _set_grads(groups, grads)
+        R.set_grads(groups, grads)
         for rs, gs in zip(refs, grads):
             for r, x in zip(rs, gs):
                 r.grad = x.clone()
@@ -192,7 +145,7 @@ def test_adam_clipping_matches_torch():
 @pytest.mark.parametrize("wdtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
 def test_adam_under_the_threshold_is_bit_identical_to_unclipped(wdtype):
     from kubeflow_controller_amd.ops.optim import FusedAdam
-    gen = torch.Generator(device=_dev()).manual_seed(3)
+    gen = torch.Generator(device=R.dev()).manual_seed(3)
     out, steps = [], None
     for max_norm in (1e4, None):
         groups = _groups(wdtype)
@@ -200,7 +153,7 @@ def test_adam_under_the_threshold_is_bit_identical_to_unclipped(wdtype):
         if steps is None:
             steps = [_rand_grads(groups, gen) for _ in range(3)]
         for grads in steps:
-            _set_grads(groups, grads)
+            R.set_grads(groups, grads)
             opt.step()
         torch.cuda.synchronize()
         if max_norm is not None:
@@ -219,7 +172,7 @@ def test_graph_replay_lamb_clip_matches_eager():
     from kubeflow_controller_amd.trainer.engine import DistInfo, Engine
     torch.manual_seed(2)
     base = MnistMLP(100)
-    d = _dev()
+    d = R.dev()
 
     def mk(optimizer="lamb", max_grad_norm=1.0):
         return Engine(copy.deepcopy(base), lambda m, x, y: cross_entropy(m(x).float(), y), optimizer=optimizer,

@@ -3,12 +3,13 @@ ranks, through a checkpoint round trip, through the replica's flags, and the
 configurations that are refused."""
 import os
 import re
-import socket
 import sys
 
 import pytest
 import torch
 import torch.multiprocessing as mp
+
+import _optim_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -18,38 +19,8 @@ SHAPES_B = [(11,), (768,)]
 HP = dict(lr=0.1, momentum=0.9, wd=0.01, trust=0.1, eps=1e-8)
 
 
-def _ref_clip(grads, gscale, max_norm):
-    """(pre-clip norm, coefficient) of torch.nn.utils.clip_grad_norm_ in fp64; coefficient 1 without max_norm."""
-    norm = gscale * torch.sqrt(sum(g.double().pow(2).sum() for g in grads))
-    if max_norm is None:
-        return norm, 1.0
-    return norm, min(1.0, float(max_norm / (norm + 1e-6)))
-
-
-def _ref_lars_step(w, mom, g, *, lr, momentum, wd, trust, eps, nesterov, adapt, gs):
-    """One LARS step of one tensor in fp64, in place; gs = gscale * clip.  Returns the rate."""
-    g = g.double() * gs
-    wn, gn = float(w.norm()), float(g.norm())
-    lam = trust * wn / (gn + wd * wn + eps) if (adapt and wn > 0 and gn > 0) else 1.0
-    d = lam * (g + wd * w)
-    mom.mul_(momentum).add_(d)
-    w.sub_(lr * (d + momentum * mom if nesterov else mom))
-    return lam
-
-
-def _groups(pad_to=64):
-    from kubeflow_controller_amd.parallel.flat import FlatGroup
-    torch.manual_seed(7)
-    pw = [torch.nn.Parameter(torch.randn(*s)) for s in SHAPES_W]
-    pb = [torch.nn.Parameter(torch.randn(*s)) for s in SHAPES_B]
-    return (FlatGroup(pw, pad_to=pad_to, name="weights"), FlatGroup(pb, pad_to=pad_to, name="norms_biases"))
-
-
-def _pad_mask(g):
-    mask = torch.ones(g.numel, dtype=torch.bool)
-    for o, p in zip(g.offsets, g.params):
-        mask[o:o + p.numel()] = False
-    return mask
+def _groups():
+    return R.cpu_groups(SHAPES_W, SHAPES_B)
 
 
 @pytest.mark.parametrize("nesterov", [False, True], ids=["plain", "nesterov"])
@@ -65,17 +36,14 @@ def test_cpu_lars_matches_fp64_reference(max_norm, nesterov):
     gen = torch.Generator().manual_seed(11)
     for _ in range(4):
         grads = [[torch.randn(p.shape, generator=gen) for p in g.params] for g in (gw, gb)]
-        for g, gs in zip((gw, gb), grads):
-            g.zero_grad()
-            for p, x in zip(g.params, gs):
-                p.grad.copy_(x)
+        R.set_grads((gw, gb), grads)
         opt.step(grad_scale=0.5)
-        norm, coef = _ref_clip([x for gs in grads for x in gs], 0.5, max_norm)
-        lams = [_ref_lars_step(ref[0][k], rm[0][k], grads[0][k].flatten(), **HP, nesterov=nesterov, adapt=True,
-                               gs=0.5 * coef) for k in range(len(ref[0]))]
+        norm, coef = R.ref_clip([x for gs in grads for x in gs], 0.5, max_norm)
+        lams = [R.ref_lars_step(ref[0][k], rm[0][k], grads[0][k].flatten(), **HP, nesterov=nesterov, adapt=True,
+                                gs=0.5 * coef) for k in range(len(ref[0]))]
         for k in range(len(ref[1])):
-            _ref_lars_step(ref[1][k], rm[1][k], grads[1][k].flatten(), **{**HP, "wd": 0.0}, nesterov=nesterov,
-                           adapt=False, gs=0.5 * coef)
+            R.ref_lars_step(ref[1][k], rm[1][k], grads[1][k].flatten(), **{**HP, "wd": 0.0}, nesterov=nesterov,
+                            adapt=False, gs=0.5 * coef)
         torch.testing.assert_close(opt.trust_ratios[0].double(), torch.tensor(lams, dtype=torch.float64),
                                    rtol=1e-5, atol=0)
         if max_norm is not None:
@@ -83,15 +51,7 @@ def test_cpu_lars_matches_fp64_reference(max_norm, nesterov):
             torch.testing.assert_close(opt.last_grad_norm.double(), norm, rtol=1e-5, atol=0)
     assert opt.step_count == 4
     assert opt.last_grad_norm is None or opt.last_grad_norm.dim() == 0
-    for gi, g in enumerate((gw, gb)):
-        for k, (o, p) in enumerate(zip(g.offsets, g.params)):
-            n = p.numel()
-            torch.testing.assert_close(p.detach().double().flatten(), ref[gi][k], atol=1e-4, rtol=1e-4)
-            torch.testing.assert_close(opt.mom[gi][o:o + n].double(), rm[gi][k], atol=1e-4, rtol=1e-4)
-        pad = _pad_mask(g)
-        assert pad.any()
-        for buf in (g.fp32, opt.mom[gi]):
-            assert torch.equal(buf[pad], torch.zeros(int(pad.sum())))
+    R.check_against((gw, gb), ([gw.fp32, gb.fp32], opt.mom), (ref, rm))
 
 
 def test_cpu_lars_without_adapting_groups_is_clipped_momentum_sgd():
@@ -119,36 +79,6 @@ def test_cpu_lars_without_adapting_groups_is_clipped_momentum_sgd():
 
 
 # ------------------------------------------------------------------ two gloo ranks == one process
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _model():
-    torch.manual_seed(0)
-    return torch.nn.Sequential(torch.nn.Linear(12, 32), torch.nn.ReLU(), torch.nn.Linear(32, 5))
-
-
-def _data():
-    g = torch.Generator().manual_seed(1)
-    return torch.randn(16, 12, generator=g), torch.randint(0, 5, (16,), generator=g)
-
-
-def _train(model, opt, sync, x, y, steps):
-    import torch.nn.functional as F
-    norms = []
-    for _ in range(steps):
-        for g in sync.groups:
-            g.zero_grad()
-        F.cross_entropy(model(x), y).backward()
-        opt.step(grad_scale=sync.finish())
-        norms.append(float(opt.last_grad_norm))
-    return norms
-
-
 # the clip is active on every step: the gradient norm of this model stays above 0.3
 DP_CLIP = 0.05
 DP_HP = dict(lr=0.05, momentum=0.9, weight_decay=0.01, trust=0.1)
@@ -162,14 +92,14 @@ def _dp_worker(rank, world, port, out):
     from kubeflow_controller_amd.parallel.flat import split_params
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    model = _model()
+    model = R.model()
     groups = split_params(model, None, pad_to=8 * world)
     broadcast_params(groups)
     sync = GradSync(groups, bucket_mb=0.0005)  # several buckets
     opt = FusedLARS(sync.spaces(), max_grad_norm=DP_CLIP, **DP_HP)
-    x, y = _data()
+    x, y = R.data()
     n = x.shape[0] // world
-    norms = _train(model, opt, sync, x[rank * n:(rank + 1) * n], y[rank * n:(rank + 1) * n], 5)
+    norms = R.train(model, opt, sync, x[rank * n:(rank + 1) * n], y[rank * n:(rank + 1) * n], 5)
     torch.save({"sd": {k: v.clone() for k, v in model.state_dict().items()}, "norms": norms,
                 "ratios": [r.clone() for r in opt.trust_ratios if r is not None],
                 "buckets": len(sync.buckets)}, f"{out}.{rank}")
@@ -182,12 +112,12 @@ def test_dp_lars_clip_matches_single_process(tmp_path):
     from kubeflow_controller_amd.parallel.ddp import GradSync
     from kubeflow_controller_amd.parallel.flat import split_params
     out = str(tmp_path / "res")
-    mp.start_processes(_dp_worker, args=(2, _free_port(), out), nprocs=2, join=True, start_method="spawn")
-    model = _model()
+    mp.start_processes(_dp_worker, args=(2, R.free_port(), out), nprocs=2, join=True, start_method="spawn")
+    model = R.model()
     before = {k: v.clone() for k, v in model.state_dict().items()}
     sync = GradSync(split_params(model, None))
     opt = FusedLARS(sync.spaces(), max_grad_norm=DP_CLIP, **DP_HP)
-    norms = _train(model, opt, sync, *_data(), 5)
+    norms = R.train(model, opt, sync, *R.data(), 5)
     assert min(norms) > 2 * DP_CLIP, norms
     ratios = [r for r in opt.trust_ratios if r is not None]
     assert ratios and all(float((r - 1).abs().min()) > 0.1 for r in ratios)  # the rates are not the neutral 1
@@ -208,13 +138,13 @@ def _engine(**kw):
     from kubeflow_controller_amd.trainer.engine import DistInfo, Engine
     import torch.nn.functional as F
     kw.setdefault("optimizer", "lars")
-    return Engine(_model(), lambda m, x, y: F.cross_entropy(m(x), y), lr=0.05, weight_decay=0.01, compute_dtype=None,
+    return Engine(R.model(), lambda m, x, y: F.cross_entropy(m(x), y), lr=0.05, weight_decay=0.01, compute_dtype=None,
                   channels_last=False, dist_info=kw.pop("dist_info", DistInfo()), **kw)
 
 
 def test_lars_engine_checkpoint_round_trip_continues_bit_identically(tmp_path):
     from kubeflow_controller_amd.ops.optim import FusedLARS
-    x, y = _data()
+    x, y = R.data()
     kw = dict(max_grad_norm=DP_CLIP, trust_coefficient=0.1, nesterov=True)
     a = _engine(**kw)
     assert isinstance(a.opt, FusedLARS) and a.opt.max_grad_norm == DP_CLIP and not a.opt_overlap

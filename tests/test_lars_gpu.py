@@ -12,6 +12,8 @@ import functools
 import pytest
 import torch
 
+import _optim_ref as R
+
 pytestmark = pytest.mark.gpu
 
 # 5: under one vector; 63x33: several vectors and numel % 8 != 0 (64x33, from the LAMB tests, is a
@@ -22,10 +24,6 @@ SHAPES_B = [(11,), (768,)]
 # lr and trust large enough that a wrong rate shows: at trust = 0.001 a whole update is below atol
 HP = dict(lr=0.1, momentum=0.9, wd=0.01, trust=0.1, eps=1e-8)
 ATOL = RTOL = 1e-4
-
-
-def _dev():
-    return torch.device("cuda")
 
 
 def _numel(shape):
@@ -48,52 +46,16 @@ def _inputs(seed, shapes_w, nsteps):
 def _groups(wdtype, init, edit=None):
     """Two flat groups with a group tail (pad_to=64): "weights" in ``wdtype`` (bf16: with an
     fp32 master and a bf16 compute copy, bf16 gradients) and fp32 1-D "norms_biases"."""
-    from kubeflow_controller_amd.parallel.flat import FlatGroup
-    pw = [torch.nn.Parameter(x.to(_dev()).to(wdtype)) for x in init[0]]
-    pb = [torch.nn.Parameter(x.to(_dev())) for x in init[1]]
+    pw = [torch.nn.Parameter(x.to(R.dev()).to(wdtype)) for x in init[0]]
+    pb = [torch.nn.Parameter(x.to(R.dev())) for x in init[1]]
     if edit is not None:
         edit(pw)
-    return FlatGroup(pw, pad_to=64, name="weights"), FlatGroup(pb, pad_to=64, name="norms_biases")
+    return R.flat_pair(pw, pb)
 
 
 def _cast_grads(groups, grads):
     """Per group, per tensor: the gradients rounded to the group's gradient dtype, on the device."""
-    return [[x.to(_dev()).to(g.grad.dtype) for x in gs] for g, gs in zip(groups, grads)]
-
-
-def _set_grads(groups, grads):
-    for g, gs in zip(groups, grads):
-        g.zero_grad()
-        for p, x in zip(g.params, gs):
-            p.grad.copy_(x)
-
-
-def _pad_mask(g):
-    mask = torch.ones(g.numel, dtype=torch.bool, device=g.device)
-    for o, p in zip(g.offsets, g.params):
-        mask[o:o + p.numel()] = False
-    return mask
-
-
-def _ref_clip(grads, gscale, max_norm):
-    norm = gscale * torch.sqrt(sum(g.double().pow(2).sum() for g in grads))
-    if max_norm is None:
-        return norm, 1.0
-    return norm, min(1.0, float(max_norm / (norm + 1e-6)))
-
-
-def _ref_lars_step(w, mom, g, *, lr, momentum, wd, trust, eps, nesterov, adapt, gs, lam_scale=1.0):
-    """One LARS step of one tensor in fp64, in place; gs = gscale * clip.  Returns the rate
-    (``lam_scale``: a deliberately wrong rate, for the sharpness check)."""
-    g = g.double() * gs
-    wn, gn = float(w.norm()), float(g.norm())
-    lam = trust * wn / (gn + wd * wn + eps) if (adapt and wn > 0 and gn > 0) else 1.0
-    if adapt:
-        lam *= lam_scale
-    d = lam * (g + wd * w)
-    mom.mul_(momentum).add_(d)
-    w.sub_(lr * (d + momentum * mom if nesterov else mom))
-    return lam
+    return [[x.to(R.dev()).to(g.grad.dtype) for x in gs] for g, gs in zip(groups, grads)]
 
 
 def _reference(w0, steps, *, wd, nesterov, gscale, max_norm, lam_scale=1.0):
@@ -103,13 +65,13 @@ def _reference(w0, steps, *, wd, nesterov, gscale, max_norm, lam_scale=1.0):
     mom = [[torch.zeros_like(x) for x in ws] for ws in w]
     lams, norms = [], []
     for grads in steps:
-        norm, coef = _ref_clip([x for gs in grads for x in gs], gscale, max_norm)
+        norm, coef = R.ref_clip([x for gs in grads for x in gs], gscale, max_norm)
         norms.append(norm)
-        lams.append([_ref_lars_step(w[0][k], mom[0][k], grads[0][k].flatten(), **{**HP, "wd": wd}, nesterov=nesterov,
-                                    adapt=True, gs=gscale * coef, lam_scale=lam_scale) for k in range(len(w[0]))])
+        lams.append([R.ref_lars_step(w[0][k], mom[0][k], grads[0][k].flatten(), **{**HP, "wd": wd}, nesterov=nesterov,
+                                     adapt=True, gs=gscale * coef, lam_scale=lam_scale) for k in range(len(w[0]))])
         for k in range(len(w[1])):
-            _ref_lars_step(w[1][k], mom[1][k], grads[1][k].flatten(), **{**HP, "wd": 0.0}, nesterov=nesterov,
-                           adapt=False, gs=gscale * coef)
+            R.ref_lars_step(w[1][k], mom[1][k], grads[1][k].flatten(), **{**HP, "wd": 0.0}, nesterov=nesterov,
+                            adapt=False, gs=gscale * coef)
     return w, mom, lams, norms
 
 
@@ -118,19 +80,7 @@ def _flat_weights(groups):
 
 
 def _check_against(groups, opt, ref_w, ref_mom):
-    """w, mom per tensor, the bf16 copy where there is one, and the padding, which must hold exact zeros."""
-    for gi, g in enumerate(groups):
-        for k, (o, p) in enumerate(zip(g.offsets, g.params)):
-            n = p.numel()
-            for got, want in ((g.fp32[o:o + n], ref_w[gi][k]), (opt.mom[gi][o:o + n], ref_mom[gi][k])):
-                assert torch.isfinite(got).all()
-                torch.testing.assert_close(got.double(), want, atol=ATOL, rtol=RTOL)
-            if g.master is not None:
-                torch.testing.assert_close(p.detach().flatten().double(), ref_w[gi][k], atol=2e-2, rtol=1e-2)
-        pad = _pad_mask(g)
-        assert pad.any()
-        for buf in (g.fp32, opt.mom[gi], g.data.float()):
-            assert torch.count_nonzero(buf[pad]) == 0, "padding must stay exactly 0"
+    R.check_against(groups, ([g.fp32 for g in groups], opt.mom), (ref_w, ref_mom), atol=ATOL, rtol=RTOL)
 
 
 def _opt(groups, **kw):
@@ -164,7 +114,7 @@ def test_lars_matches_fp64_reference(wdtype, max_norm, nesterov):
         assert float((a - b).abs().max()) > 10 * ATOL, (k, float((a - b).abs().max()))
     got_lams, got_norms = [], []
     for grads in steps:
-        _set_grads(groups, grads)
+        R.set_grads(groups, grads)
         opt.step(grad_scale=0.5)
         got_lams.append(opt.trust_ratios[0].clone())
         got_norms.append(opt.last_grad_norm.clone() if max_norm is not None else None)
@@ -177,7 +127,7 @@ def test_lars_matches_fp64_reference(wdtype, max_norm, nesterov):
     if max_norm is None:
         assert opt.last_grad_norm is None
     else:
-        assert _ref_clip([x for gs in steps[-1] for x in gs], 0.5, max_norm)[1] < 0.1  # the clip was active
+        assert R.ref_clip([x for gs in steps[-1] for x in gs], 0.5, max_norm)[1] < 0.1  # the clip was active
         for got, want in zip(got_norms, norms):
             torch.testing.assert_close(got.double(), want, rtol=1e-5, atol=0)
 
@@ -200,7 +150,7 @@ def test_lars_rate_edge_cases():
     ref_w, ref_mom, lams, _ = _reference(w0, steps, wd=0.0, nesterov=False, gscale=1.0, max_norm=None)
     assert lams[0][0] == 1.0 and all(l[1] == 1.0 for l in lams) and all(l[2] != 1.0 for l in lams)
     for i, grads in enumerate(steps):
-        _set_grads(groups, grads)
+        R.set_grads(groups, grads)
         opt.step()
         got = opt.trust_ratios[0].tolist()
         assert got[1] == 1.0 and (i > 0 or got[0] == 1.0)
@@ -220,7 +170,7 @@ def test_lars_step_is_bit_repeatable():
         groups = _groups(torch.bfloat16, init)
         opt = _opt(groups, max_grad_norm=1.0)
         for grads in [_cast_grads(groups, g) for g in raw]:
-            _set_grads(groups, grads)
+            R.set_grads(groups, grads)
             opt.step()
         torch.cuda.synchronize()
         assert float(opt.last_grad_norm) > 10.0  # clipping active
@@ -249,7 +199,7 @@ def test_lars_without_adapting_groups_is_bit_identical_to_sgd(wdtype, nesterov, 
             opt = FusedSGD(groups, lr=HP["lr"], momentum=HP["momentum"], dampening=0.0, weight_decay=HP["wd"],
                            nesterov=nesterov)
         for grads in [_cast_grads(groups, g) for g in raw]:
-            _set_grads(groups, grads)
+            R.set_grads(groups, grads)
             opt.step(grad_scale=0.5)
         torch.cuda.synchronize()
         if kind == "lars" and max_norm is not None:
@@ -269,7 +219,7 @@ def test_graph_replay_lars_clip_matches_eager():
     from kubeflow_controller_amd.trainer.engine import DistInfo, Engine
     torch.manual_seed(2)
     base = MnistMLP(100)
-    d = _dev()
+    d = R.dev()
 
     def mk(optimizer="lars", max_grad_norm=1.0, **kw):
         return Engine(copy.deepcopy(base), lambda m, x, y: cross_entropy(m(x).float(), y), optimizer=optimizer,
