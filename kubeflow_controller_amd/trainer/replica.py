@@ -137,8 +137,12 @@ def build(args, device):
         return mnist.MnistMLP(args.hidden_units), data, lambda m, x, y: xent(m(x).float(), y)
     if name in ("resnet50", "resnet_tiny"):
         from ..models.resnet import resnet50, resnet_tiny
-        model = resnet50() if name == "resnet50" else resnet_tiny(10)
-        return model, None, lambda m, x, y: cross_entropy(m(x), y)
+        data = image_dataset(args)  # None without a dataset directory: the synthetic batch
+        if data is not None:
+            model = resnet50(data.num_classes) if name == "resnet50" else resnet_tiny(data.num_classes)
+        else:
+            model = resnet50() if name == "resnet50" else resnet_tiny(10)
+        return model, data, lambda m, x, y: cross_entropy(m(x), y)
     if name in ("bert_base", "bert_tiny"):
         from ..models.bert import BertConfig, BertForPreTraining, bert_loss
         cfg = BertConfig.base() if name == "bert_base" else BertConfig.tiny()
@@ -152,6 +156,40 @@ def build(args, device):
             else None
         return WideDeep(cfg, device=device), None, wide_deep_loss
     raise SystemExit(f"unknown --model {name}")
+
+
+def image_dataset(args):
+    """The ``ImageDataset`` of ``--data_dir`` for the ResNet models, or None when the
+    directory is empty, absent or holds no ``train_images.npy`` (synthetic batch)."""
+    from ..models import imagenet
+    d = getattr(args, "data_dir", "")
+    if not args.model.startswith("resnet") or not imagenet.has_dataset(d):
+        return None
+    s = getattr(args, "image_size", 0) or (224 if args.model == "resnet50" else 32)
+    gb = getattr(args, "data_resident_gb", -1.0)
+    return imagenet.ImageDataset(d, (s, s), augment=getattr(args, "augment", "rrc"),
+                                 crop_pad=getattr(args, "crop_pad", 4), seed=args.seed,
+                                 data_resident_gb=None if gb is None or gb < 0 else gb)
+
+
+def _place_images(data, device, rank: int, world: int, step: int, bf16: bool) -> None:
+    """Shard, place (resident or staged) and position an ``ImageDataset`` for this replica."""
+    data.set_shard(rank, world)
+    data.dtype = torch.bfloat16 if (device.type == "cuda" and bf16) else torch.float32
+    data.to(device)
+    data.set_step(step)
+    _log(f"data ready: {data.describe()}")
+    _log(f"Worker {rank}: training images {'resident on ' + str(device) if data.resident else 'staged per batch'}, "
+         f"augment {data.augment}, {data.num_classes} classes, input {data.out_hw[0]}x{data.out_hw[1]}, "
+         f"next batch: step {step}")
+
+
+def _validate_images(model, data, batch_size: int) -> None:
+    from ..models.imagenet import evaluate
+    with torch.no_grad():
+        model.eval()
+        acc, ce, m = evaluate(model, data.eval_batches(batch_size))
+    _log(f"Validation: top-1 accuracy = {acc:.4f}, cross entropy = {ce:g} over {m} images")
 
 
 def synthetic_batch(args, model, device, rank: int):
@@ -324,6 +362,8 @@ def run_worker_async(spec: ClusterSpec, args) -> int:
          f"{'sync replicas (%d of %d aggregated)' % (agg, W) if agg else 'async'} parameter server "
          f"({transport if transport.endswith(')') else transport + ' transport'})")
     fixed = None if data is not None else synthetic_batch(args, model, device, spec.task_index)
+    if hasattr(data, "eval_batches"):
+        _place_images(data, device, spec.task_index, W, 0, bool(use_gpu and args.bf16))
     t_begin = time.time()
     _log(f"Training begins @ {t_begin:f}")
     local_step, global_step, t_first, loss = 0, 0, None, None
@@ -357,7 +397,13 @@ def run_worker_async(spec: ClusterSpec, args) -> int:
     client.pull()  # evaluate the PS's current variables, as the reference's session does
     client.done()
     client.close()
-    if data is not None:
+    if hasattr(data, "eval_batches"):
+        if loss is not None:
+            _log(f"Final loss: {float(loss):.5f}")
+        if data.val is not None:
+            _validate_images(model, data, args.batch_size)
+        data.close()
+    elif data is not None:
         with torch.no_grad():
             model.eval()
             vx, vy = data.validation
@@ -488,7 +534,9 @@ def run_worker(spec: ClusterSpec, args) -> int:
     # 21.8 ms eager, replay measured 0.5 % slower; the reference's MNIST: 0.2 ms).
     use_graph = args.graph == "on" or (args.graph == "auto" and world == 1 and device.type == "cuda")
     cap_step = 1 if args.graph == "on" else 2
-    if data is not None and device.type == "cuda" and hasattr(data, "to"):
+    if hasattr(data, "eval_batches"):  # image dataset: resident in HBM or staged through pinned buffers
+        _place_images(data, device, rank, world, resumed // inc, bool(use_gpu and args.bf16))
+    elif data is not None and device.type == "cuda" and hasattr(data, "to"):
         data.to(device)  # dataset resident in HBM: no host copy per step
     # steady-state window: from the end of the warm-up steps (step 0 tunes the
     # per-shape kernels, the capture step records the graph), GPU drained first
@@ -538,7 +586,13 @@ def run_worker(spec: ClusterSpec, args) -> int:
     if t_first is not None and steps_per_worker > warm:
         sps = (steps_per_worker - warm) / max(t_end - t_first, 1e-9)
         _log(f"Steady-state: {sps:.1f} steps/s/worker, {sps * args.batch_size * world:.1f} examples/s (job)")
-    if data is not None:
+    if hasattr(data, "eval_batches"):
+        if loss is not None:
+            _log(f"Final loss: {float(loss):.5f}")
+        if data.val is not None:
+            _validate_images(model, data, args.batch_size)
+        data.close()
+    elif data is not None:
         with torch.no_grad():
             model.eval()
             vx, vy = data.validation
@@ -609,7 +663,19 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--download_only", type=_flag, nargs="?", const=True, default=False,
                     help="prepare the data set and exit 0 (synthetic data: nothing to download)")
     ap.add_argument("--num_gpus", type=int, default=1, help="accepted (one GPU per replica)")
-    ap.add_argument("--data_dir", default="", help="accepted (synthetic data; no network)")
+    ap.add_argument("--data_dir", default="",
+                    help="resnet50 / resnet_tiny: a directory with train_images.npy (uint8 [N, H, W, 3]) and "
+                         "train_labels.npy (int64 [N]), optionally val_*.npy and meta.json (docs/get_started.md); "
+                         "empty, absent or without that file: synthetic data, as for every other model")
+    ap.add_argument("--image_size", type=int, default=0,
+                    help="network input size with --data_dir (default: 224 for resnet50, 32 for resnet_tiny)")
+    ap.add_argument("--augment", default="rrc", choices=["rrc", "crop", "none"],
+                    help="with --data_dir: rrc = random-resized-crop + flip; crop = random crop after "
+                         "--crop_pad zero padding + flip; none = centre crop (validation always uses it)")
+    ap.add_argument("--crop_pad", type=int, default=4, help="--augment crop: zero padding on every side")
+    ap.add_argument("--data_resident_gb", type=float, default=-1.0,
+                    help="device memory budget (GB) for keeping the dataset resident; below it the batches are "
+                         "staged through pinned host buffers (negative: at most half of the free device memory)")
     ap.add_argument("--model_dir", default=os.environ.get("KFA_MODEL_DIR", ""),
                     help="checkpoint / resume directory (TFJob spec.modelDir via $KFA_MODEL_DIR)")
     ap.add_argument("--checkpoint_every", type=int, default=0, help="local steps between checkpoints")
@@ -646,6 +712,8 @@ def main(argv: Optional[list] = None) -> int:
             from ..models import mnist
             d = mnist.SyntheticMNIST(seed=args.seed)
             _log(f"data ready: synthetic MNIST, {len(d.train[0])} training examples (--download_only)")
+        elif image_dataset(args) is not None:
+            _log(f"data ready: {image_dataset(args).describe()}")
         else:
             _log(f"data ready: synthetic {args.model} batches are generated in-process (--download_only)")
         return 0
