@@ -72,7 +72,10 @@ loop (``kfc_recv_any``), where the per-pair message order stands in for the tags
   another worker's still-running mailbox copy) and workers' waits covering other
   workers' updates — a host-waited header only reaches the PS once its data is
   there.  ROCm's interprocess events also stop working after 31 records
-  (``tools/probe_ipc_event4.py``), hence the event chains below.
+  (``tools/probe_ipc_event4.py``), hence the event chains below.  The runtime
+  pins each event's shared memory with ``hipHostRegister`` at its first record,
+  so where memory a process already has cannot be pinned (some virtual
+  machines) that record fails with invalid argument: leave the switch off there.
   Default (``KFA_PS_DEVICE_SIGNAL`` unset / 0): host waits on recorded events
   (the round-4 protocol).
 

@@ -2,6 +2,7 @@
 PS variables / Adam state / gradient mailboxes in GPU memory, pulls and pushes
 as device-to-device copies, only headers over gloo.  Runs every process on the
 one GPU of the box (IPC within a device works like across xGMI peers)."""
+import functools
 import os
 import socket
 import subprocess
@@ -60,6 +61,20 @@ def _proc(rank, W, P, port, out, opt, agg, sig="1", nsteps=5):
     dist.destroy_process_group()
 
 
+@functools.lru_cache(maxsize=None)
+def _interprocess_events_work():
+    """ROCm backs an interprocess event with shared memory that the runtime pins
+    with ``hipHostRegister`` at the first record; where the machine cannot pin
+    memory a process already has, that record fails with invalid argument."""
+    try:
+        torch.cuda.Event(interprocess=True).record()
+    except RuntimeError as e:
+        if "invalid argument" not in str(e):
+            raise
+        return False
+    return True
+
+
 @pytest.mark.parametrize("sig", ["1", "0"], ids=["device_signal", "host_waits"])
 @pytest.mark.parametrize("opt,agg,nsteps", [("sgd", 0, 5), ("adam", 0, 5), ("adam", 2, 5), ("sgd", 0, 40)],
                          ids=["sgd", "adam", "adam_agg2", "sgd_long"])
@@ -70,6 +85,8 @@ def test_device_async_ps_matches_host_server(tmp_path, opt, agg, sig, nsteps):
     the PS memory (canary check passed: device transport, no host fallback).
     ``sgd_long``: 80 updates per PS, so the device-signalling event chains roll
     over five generations (ROCm's interprocess events fail after 31 records)."""
+    if sig == "1" and not _interprocess_events_work():
+        pytest.skip("HIP interprocess events cannot be recorded here (the runtime's hipHostRegister is not supported)")
     from kubeflow_controller_amd.parallel.async_ps import AsyncPSServer
     W, P = 2, 2
     out = str(tmp_path / "dps")
