@@ -1118,6 +1118,561 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_long_kernel(
   store_tile(st, dqkv, q0 + qb, W3, h * AD, dbqkv, lane);
 }
 
+// ============================================================================
+// Packed variable-length batches: qkv [T, 3H] holds B sequences back to back,
+// sequence i owns rows cu[i] .. cu[i+1]-1 (any length 1..8192, any start), rows
+// cu[B] .. T-1 are unowned (row-budget padding: never read, written as zeros).
+// There is no key bias — a packed batch has no padded keys.
+//
+// A workgroup owns (sequence, head, 128-row block); the grid is sized from the
+// host's max_seqlen, a workgroup whose block starts past its sequence exits before
+// any barrier, and every key / query loop runs ceil(len / 128) blocks.  Unlike the
+// long kernels, only the STREAMED operand lives in LDS (32 KiB per workgroup):
+//   forward   K, V images; the wave's 32 query rows are MFMA operands read straight
+//             from memory into registers, P feeds P·V from registers (rd_tr2 on V,
+//             as the S = 128 forward), O is staged in the K image at the end;
+//   dK / dV   Q, dO images; the wave's 32 keys (K and V) are register operands;
+//   dQ        K, V images; the wave's Q and dO rows are register operands.
+// Rows at or past the sequence end are zero in the images and in the register
+// operands and are never loaded (the neighbour sequence, or past the tensor, lies
+// there).  len is uniform per workgroup, so work follows the live tokens: no MFMA
+// is issued for a 16-key score tile, a 32-key P·V / dQ slice or a 32-query dK/dV
+// step that lies wholly past len, and a wave whose 32-row slice is wholly past
+// len only helps load the images and takes the barriers.
+// Dropout: attn_pair_hash(seed, h·T + global query row, max_seqlen, key within its
+// sequence with bit 4 clear) — the same decisions in all three kernels.
+constexpr float kMasked = -3.0e38f;
+// the packed-varlen kernels are compiled without the packed fp32 VALU forms
+#define KFA_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+
+// one 16x16x32 operand row piece straight from memory: 8 columns at src (+ bias)
+// (· scale); a row that does not exist is zero and is not loaded
+template <bool BIAS>
+__device__ __forceinline__ short8 row_operand(const bf16_t* __restrict__ src, bool live, const float* __restrict__ bias,
+                                              float scale) {
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (live) {
+    v = *reinterpret_cast<const uint4*>(src);
+    if constexpr (BIAS) {
+      const float4 b0 = *reinterpret_cast<const float4*>(bias), b1 = *reinterpret_cast<const float4*>(bias + 4);
+      const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+      float f[8];
+      unpack8(v, f);
+#pragma unroll
+      for (int e = 0; e < 8; e++) f[e] = (f[e] + bb[e]) * scale;
+      v = pack8(f);
+    }
+  }
+  return *reinterpret_cast<const short8*>(&v);
+}
+
+// NI [128 rows][64] images as images_issue / images_commit, but only rows < live are
+// loaded (and transformed); the others are zero in the image
+template <int NI>
+__device__ __forceinline__ void tail_images(const bf16_t* const (&src)[NI], const long (&ld)[NI], long row0,
+                                            const int (&col)[NI], const float* __restrict__ bias,
+                                            const bool (&transform)[NI], const float (&scale)[NI], int live,
+                                            char* const (&img)[NI], int tid) {
+  const int r0 = tid >> 3, c = tid & 7;
+  float bb[NI][8];
+  uint4 raw[NI][4];
+#pragma unroll
+  for (int i = 0; i < NI; i++)
+    if (transform[i]) {  // compile-time after unrolling
+      const float4 b0 = *reinterpret_cast<const float4*>(bias + col[i] + c * 8);
+      const float4 b1 = *reinterpret_cast<const float4*>(bias + col[i] + c * 8 + 4);
+      bb[i][0] = b0.x; bb[i][1] = b0.y; bb[i][2] = b0.z; bb[i][3] = b0.w;
+      bb[i][4] = b1.x; bb[i][5] = b1.y; bb[i][6] = b1.z; bb[i][7] = b1.w;
+    }
+#pragma unroll
+  for (int i = 0; i < NI; i++)
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      raw[i][k] = make_uint4(0u, 0u, 0u, 0u);
+      if (r0 + 32 * k < live)
+        raw[i][k] = *reinterpret_cast<const uint4*>(src[i] + (row0 + r0 + 32 * k) * ld[i] + col[i] + c * 8);
+    }
+#pragma unroll
+  for (int i = 0; i < NI; i++)
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      uint4 v = raw[i][k];
+      if (transform[i] && r0 + 32 * k < live) {
+        float f[8];
+        unpack8(v, f);
+#pragma unroll
+        for (int e = 0; e < 8; e++) f[e] = (f[e] + bb[i][e]) * scale[i];
+        v = pack8(f);
+      }
+      *reinterpret_cast<uint4*>(img[i] + off64(r0 + 32 * k, c * 8)) = v;
+    }
+}
+
+// zeros into columns colb..colb+63 of rows r0..r1-1 (the unowned rows), whole workgroup
+__device__ __forceinline__ void zero_rows(bf16_t* __restrict__ dst, long ld, int colb, long r0, long r1, int tid) {
+  for (long r = r0 + (tid >> 3); r < r1; r += 32)
+    *reinterpret_cast<uint4*>(dst + r * ld + colb + (tid & 7) * 8) = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// store_tile for a tile whose rows >= nrows do not exist: they are neither stored nor summed
+__device__ __forceinline__ void store_tile_rows(const char* st, bf16_t* __restrict__ dst, long row0, long ld, int colb,
+                                                int nrows, float* __restrict__ dbias, int lane) {
+  const int c = lane & 7;
+  float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int it = 0; it < 4; it++) {
+    const int r = it * 8 + (lane >> 3);
+    if (r < nrows) {
+      const uint4 v = *reinterpret_cast<const uint4*>(st + off64(r, c * 8));
+      *reinterpret_cast<uint4*>(dst + (row0 + r) * ld + colb + c * 8) = v;
+      float f[8];
+      unpack8(v, f);
+#pragma unroll
+      for (int e = 0; e < 8; e++) cs[e] += f[e];
+    }
+  }
+  if (dbias) {
+#pragma unroll
+    for (int o = 8; o < 64; o <<= 1)
+#pragma unroll
+      for (int e = 0; e < 8; e++) cs[e] += __shfl_xor(cs[e], o, 64);
+    if (lane < 8)
+#pragma unroll
+      for (int e = 0; e < 8; e++) atomicAdd(dbias + colb + c * 8 + e, cs[e]);
+  }
+}
+
+// the workgroup's place in the packed batch; false: its block starts past its sequence
+struct VarBlock {
+  int blk, b, h, s0, len;
+};
+__device__ __forceinline__ bool var_block(const int* __restrict__ cu, int T, int heads, int max_seqlen, VarBlock& w) {
+  const int nb = (max_seqlen + BLK - 1) / BLK;
+  const int sh = blockIdx.x / nb;
+  w.blk = blockIdx.x - sh * nb;
+  w.b = sh / heads;
+  w.h = sh - w.b * heads;
+  w.s0 = max(cu[w.b], 0);
+  w.len = min(cu[w.b + 1], T) - w.s0;  // a table the host validated; the clamps only keep a stale one in bounds
+  return w.blk * BLK < w.len;
+}
+
+__global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_varlen_fwd_kernel(const bf16_t* __restrict__ qkv,
+                                                                 const float* __restrict__ bqkv,
+                                                                 const int* __restrict__ cu, bf16_t* __restrict__ out,
+                                                                 float* __restrict__ lse, int B, int T, int heads,
+                                                                 int max_seqlen, float qscale, uint32_t thresh,
+                                                                 float dscale, uint64_t seed) {
+  __shared__ __attribute__((aligned(16))) char sm[2 * 16384];  // K, V images (32 KiB)
+  char* Ki = sm;
+  char* Vi = sm + 16384;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
+  VarBlock w;
+  if (!var_block(cu, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
+  const int h = w.h, H = heads * AD;
+  const long W3 = 3L * H, q0 = (long)w.s0 + (long)w.blk * BLK;
+  if (w.blk == 0 && w.b == B - 1) zero_rows(out, H, h * AD, (long)w.s0 + w.len, T, tid);
+  const int qlive = min(BLK, w.len - w.blk * BLK), nkb = (w.len + BLK - 1) / BLK;
+  const int qb = wave * 32;
+  const bool wlive = qb < qlive;  // else: this wave's queries do not exist
+  short8 qreg[2][2] = {};
+  if (wlive) {
+#pragma unroll
+    for (int qt = 0; qt < 2; qt++)
+#pragma unroll
+      for (int ks = 0; ks < 2; ks++) {
+        const int row = qb + 16 * qt + fr, c = h * AD + ks * 32 + fq * 8;
+        // scores in log2 units: the softmax exponent is one subtraction + v_exp_f32
+        qreg[qt][ks] = row_operand<true>(qkv + (q0 + row) * W3 + c, row < qlive, bqkv + c, qscale * kLog2e);
+      }
+  }
+  float m[2] = {kMasked, kMasked}, l[2] = {0.f, 0.f};
+  floatx4 o[4][2];
+#pragma unroll
+  for (int dt = 0; dt < 4; dt++) o[dt][0] = o[dt][1] = floatx4{0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < nkb; j++) {
+    const int klive = min(BLK, w.len - j * BLK);  // >= 1
+    if (j > 0) __syncthreads();  // every wave is done with key block j-1
+    {
+      const int col[2] = {H + h * AD, 2 * H + h * AD};
+      const bool tf[2] = {true, true};
+      const float sc[2] = {1.f, 1.f};
+      char* const img[2] = {Ki, Vi};
+      const bf16_t* const src[2] = {qkv, qkv};
+      const long ld[2] = {W3, W3};
+      tail_images<2>(src, ld, (long)w.s0 + (long)j * BLK, col, bqkv, tf, sc, klive, img, tid);
+    }
+    __syncthreads();
+    if (!wlive) continue;
+    // s[kt][qt][r] = score(q = qb + 16qt + fr, key = 16kt + 4fq + r); dead key tiles stay 0 until masked
+    floatx4 s[8][2];
+#pragma unroll
+    for (int kt = 0; kt < 8; kt++) {
+      s[kt][0] = s[kt][1] = floatx4{0.f, 0.f, 0.f, 0.f};
+      if (kt * 16 < klive) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+          const short8 a = rd_row<64>(Ki, kt * 16 + fr, ks * 32 + fq * 8);
+          s[kt][0] = mma(a, qreg[0][ks], s[kt][0]);
+          s[kt][1] = mma(a, qreg[1][ks], s[kt][1]);
+        }
+      }
+    }
+    if (klive < BLK) {
+#pragma unroll
+      for (int kt = 0; kt < 8; kt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+          if (kt * 16 + 4 * fq + r >= klive) s[kt][0][r] = s[kt][1][r] = kMasked;
+    }
+#pragma unroll
+    for (int qt = 0; qt < 2; qt++) {
+      float mx = kMasked;
+#pragma unroll
+      for (int kt = 0; kt < 8; kt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) mx = fmaxf(mx, s[kt][qt][r]);
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float mn = fmaxf(m[qt], mx);  // finite: key 0 of every block is live
+      const float alpha = __builtin_amdgcn_exp2f(m[qt] - mn);
+      float sum = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < 8; kt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const float e = __builtin_amdgcn_exp2f(s[kt][qt][r] - mn);
+          s[kt][qt][r] = e;
+          sum += e;
+        }
+      sum += __shfl_xor(sum, 16, 64);
+      sum += __shfl_xor(sum, 32, 64);
+      l[qt] = l[qt] * alpha + sum;
+      m[qt] = mn;
+#pragma unroll
+      for (int dt = 0; dt < 4; dt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) o[dt][qt][r] *= alpha;
+      if (thresh) {
+        const uint64_t row = (uint64_t)h * T + (uint64_t)(q0 + qb + qt * 16 + fr);
+#pragma unroll
+        for (int kp = 0; kp < 4; kp++)
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const uint32_t hh = attn_pair_hash(seed, row, max_seqlen, j * BLK + 32 * kp + 4 * fq + r);
+            s[2 * kp][qt][r] = keep_lo(hh, thresh) ? s[2 * kp][qt][r] * dscale : 0.f;
+            s[2 * kp + 1][qt][r] = keep_hi(hh, thresh) ? s[2 * kp + 1][qt][r] * dscale : 0.f;
+          }
+      }
+    }
+    // Oᵀ += Vᵀ·Pdᵀ from registers (as attn_fwd_kernel): tiles 2ks, 2ks+1 give this lane keys
+    // {32ks + 4fq + r, 32ks + 16 + 4fq + r}, V's rows are read in the same order
+#pragma unroll
+    for (int ks = 0; ks < 4; ks++)
+      if (ks * 32 < klive) {
+        const short8 b0 = pack_pair(s[2 * ks][0], s[2 * ks + 1][0]);
+        const short8 b1 = pack_pair(s[2 * ks][1], s[2 * ks + 1][1]);
+        const int ra = 32 * ks + 4 * fq;
+#pragma unroll
+        for (int dt = 0; dt < 4; dt++) {
+          const short8 a = rd_tr2<64>(Vi, ra, ra + 16, dt * 16, lane);
+          o[dt][0] = mma(a, b0, o[dt][0]);
+          o[dt][1] = mma(a, b1, o[dt][1]);
+        }
+      }
+  }
+  __syncthreads();  // every wave is done with the K image: it becomes the O stage
+  if (!wlive) return;
+#pragma unroll
+  for (int qt = 0; qt < 2; qt++) {
+    const int q = qb + qt * 16 + fr;
+    const float inv = 1.f / l[qt];
+    if (fq == 0 && q < qlive) lse[(long)h * T + q0 + q] = (m[qt] + __log2f(l[qt])) * kLn2;  // natural-log units
+#pragma unroll
+    for (int dt = 0; dt < 4; dt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) o[dt][qt][r] *= inv;
+  }
+  char* st = Ki + wave * 4096;
+  stage_tile(st, o, 1.f, fr, fq);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  store_tile_rows(st, out, q0 + qb, H, h * AD, qlive - qb, nullptr, lane);
+}
+
+// D[h][t] = Σ_d dO[t][h·64 + d]·O[t][h·64 + d] of the owned rows t < cu[B]; one thread per (row, head)
+__global__ KFA_NO_PK_F32 void attn_varlen_rowdot_kernel(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ out,
+                                          const int* __restrict__ cu, float* __restrict__ D, int B, int T, int heads) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)min(cu[B], T) * heads) return;
+  const long tok = t / heads;
+  const int h = (int)(t - tok * heads), H = heads * AD;
+  const uint4* g = reinterpret_cast<const uint4*>(dout + tok * H + h * AD);
+  const uint4* o = reinterpret_cast<const uint4*>(out + tok * H + h * AD);
+  float acc = 0.f;
+#pragma unroll
+  for (int c = 0; c < 8; c++) {
+    float a[8], b[8];
+    unpack8(g[c], a);
+    unpack8(o[c], b);
+#pragma unroll
+    for (int e = 0; e < 8; e++) acc += a[e] * b[e];
+  }
+  D[(long)h * T + tok] = acc;
+}
+
+// key-owner dK / dV: workgroup per (sequence, head, 128-key block); wave w owns keys 32w.. of the
+// block as register operands and streams the sequence's query blocks (Q, dO images)
+__global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_varlen_bwd_kv_kernel(
+    const bf16_t* __restrict__ qkv, const float* __restrict__ bqkv, const int* __restrict__ cu,
+    const float* __restrict__ lse, const float* __restrict__ Dq, const bf16_t* __restrict__ dout,
+    bf16_t* __restrict__ dqkv, float* __restrict__ dbqkv, int B, int T, int heads, int max_seqlen, float qscale,
+    uint32_t thresh, float dscale, uint64_t seed) {
+  __shared__ __attribute__((aligned(16))) char sm[2 * 16384];  // Q, dO images (32 KiB)
+  char* Qi = sm;
+  char* Gi = sm + 16384;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
+  VarBlock w;
+  if (!var_block(cu, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
+  const int h = w.h, H = heads * AD;
+  const long W3 = 3L * H, k0 = (long)w.s0 + (long)w.blk * BLK;
+  if (w.blk == 0 && w.b == B - 1) {
+    zero_rows(dqkv, W3, H + h * AD, (long)w.s0 + w.len, T, tid);
+    zero_rows(dqkv, W3, 2 * H + h * AD, (long)w.s0 + w.len, T, tid);
+  }
+  const int klive = min(BLK, w.len - w.blk * BLK), nqb = (w.len + BLK - 1) / BLK;
+  const int kw = wave * 32;
+  const bool wlive = kw < klive;  // else: this wave's keys do not exist
+  short8 kreg[2][2] = {}, vreg[2][2] = {};
+  bool keyok[2] = {false, false};
+  if (wlive) {
+#pragma unroll
+    for (int kt = 0; kt < 2; kt++) {
+      const int row = kw + 16 * kt + fr;
+      keyok[kt] = row < klive;
+#pragma unroll
+      for (int ks = 0; ks < 2; ks++) {
+        const int c = h * AD + ks * 32 + fq * 8;
+        kreg[kt][ks] = row_operand<true>(qkv + (k0 + row) * W3 + H + c, keyok[kt], bqkv + H + c, 1.f);
+        vreg[kt][ks] = row_operand<true>(qkv + (k0 + row) * W3 + 2 * H + c, keyok[kt], bqkv + 2 * H + c, 1.f);
+      }
+    }
+  }
+  floatx4 dvT[4][2], dkT[4][2];
+#pragma unroll
+  for (int dt = 0; dt < 4; dt++) dvT[dt][0] = dvT[dt][1] = dkT[dt][0] = dkT[dt][1] = floatx4{0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < nqb; i++) {
+    const int qlive = min(BLK, w.len - i * BLK);
+    const long qrow0 = (long)w.s0 + (long)i * BLK;
+    if (i > 0) __syncthreads();  // every wave is done with the previous Q / dO images
+    {
+      const int col[2] = {h * AD, h * AD};
+      const bool tf[2] = {true, false};
+      const float sc[2] = {qscale, 1.f};
+      char* const img[2] = {Qi, Gi};
+      const bf16_t* const src[2] = {qkv, dout};
+      const long ld[2] = {W3, (long)H};
+      tail_images<2>(src, ld, qrow0, col, bqkv, tf, sc, qlive, img, tid);
+    }
+    // lse·log2(e) and D of queries lane and lane + 64 of the block (0 where there is no query)
+    float lq2[2] = {0.f, 0.f}, dd2[2] = {0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < 2; u++)
+      if (wlive && lane + 64 * u < qlive) {
+        lq2[u] = lse[(long)h * T + qrow0 + lane + 64 * u] * kLog2e;
+        dd2[u] = Dq[(long)h * T + qrow0 + lane + 64 * u];
+      }
+    __syncthreads();
+    if (!wlive) continue;
+    for (int j = 0; j < 4 && 32 * j < qlive; j++) {  // 32-query steps that hold a query
+      const float lqs = j >> 1 ? lq2[1] : lq2[0], dds = j >> 1 ? dd2[1] : dd2[0];
+      // s / dp[qt][kt][r]: (q = 32j + 16qt + 4fq + r, key = kw + 16kt + fr)
+      floatx4 s[2][2], dp[2][2];
+#pragma unroll
+      for (int qt = 0; qt < 2; qt++) s[qt][0] = s[qt][1] = dp[qt][0] = dp[qt][1] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 2; ks++)
+#pragma unroll
+        for (int qt = 0; qt < 2; qt++) {
+          const short8 aq = rd_row<64>(Qi, 32 * j + 16 * qt + fr, ks * 32 + fq * 8);
+          const short8 ag = rd_row<64>(Gi, 32 * j + 16 * qt + fr, ks * 32 + fq * 8);
+#pragma unroll
+          for (int kt = 0; kt < 2; kt++) {
+            s[qt][kt] = mma(aq, kreg[kt][ks], s[qt][kt]);
+            dp[qt][kt] = mma(ag, vreg[kt][ks], dp[qt][kt]);
+          }
+        }
+      floatx4 pd[2][2], ds[2][2];
+#pragma unroll
+      for (int qt = 0; qt < 2; qt++) {
+        const int qb4 = 32 * j + 16 * qt + 4 * fq;  // query within the block
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const float D = __shfl(dds, (qb4 + r) & 63, 64);
+          const float lq = __shfl(lqs, (qb4 + r) & 63, 64);
+          const bool qok = qb4 + r < qlive;
+          const uint32_t hh = thresh ? attn_pair_hash(seed, (uint64_t)h * T + (uint64_t)(qrow0 + qb4 + r), max_seqlen,
+                                                      w.blk * BLK + kw + fr)
+                                     : 0u;
+#pragma unroll
+          for (int kt = 0; kt < 2; kt++) {
+            // a pair with no query or no key has P = 0, whatever lse holds there
+            const float p = (qok && keyok[kt]) ? __builtin_amdgcn_exp2f(fmaf(s[qt][kt][r], kLog2e, -lq)) : 0.f;
+            float g = dp[qt][kt][r], pv = p;
+            if (thresh) {
+              const bool keep = kt ? keep_hi(hh, thresh) : keep_lo(hh, thresh);
+              pv = keep ? p * dscale : 0.f;
+              g = keep ? g * dscale : 0.f;
+            }
+            pd[qt][kt][r] = pv;
+            ds[qt][kt][r] = p * (g - D);
+          }
+        }
+      }
+      const int ra = 32 * j + 4 * fq, rb = ra + 16;
+      short8 gtr[4], qtr[4];
+#pragma unroll
+      for (int dt = 0; dt < 4; dt++) {
+        gtr[dt] = rd_tr2<64>(Gi, ra, rb, dt * 16, lane);
+        qtr[dt] = rd_tr2<64>(Qi, ra, rb, dt * 16, lane);
+      }
+#pragma unroll
+      for (int kt = 0; kt < 2; kt++) {
+        const short8 bp = pack_pair(pd[0][kt], pd[1][kt]);
+        const short8 bs = pack_pair(ds[0][kt], ds[1][kt]);
+#pragma unroll
+        for (int dt = 0; dt < 4; dt++) {
+          dvT[dt][kt] = mma(gtr[dt], bp, dvT[dt][kt]);
+          dkT[dt][kt] = mma(qtr[dt], bs, dkT[dt][kt]);
+        }
+      }
+    }
+  }
+  __syncthreads();  // the images become the output stage
+  if (!wlive) return;
+  char* st = sm + wave * 8192;
+  stage_tile(st, dkT, 1.f, fr, fq);
+  stage_tile(st + 4096, dvT, 1.f, fr, fq);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  store_tile_rows(st, dqkv, k0 + kw, W3, H + h * AD, klive - kw, dbqkv, lane);
+  store_tile_rows(st + 4096, dqkv, k0 + kw, W3, 2 * H + h * AD, klive - kw, dbqkv, lane);
+}
+
+// query-owner dQ = dS·K: workgroup per (sequence, head, 128-query block); wave w owns queries 32w..
+// (Q and dO rows as register operands) and streams the sequence's key blocks (K, V images)
+__global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_varlen_bwd_q_kernel(
+    const bf16_t* __restrict__ qkv, const float* __restrict__ bqkv, const int* __restrict__ cu,
+    const float* __restrict__ lse, const float* __restrict__ Dq, const bf16_t* __restrict__ dout,
+    bf16_t* __restrict__ dqkv, float* __restrict__ dbqkv, int B, int T, int heads, int max_seqlen, float qscale,
+    uint32_t thresh, float dscale, uint64_t seed) {
+  __shared__ __attribute__((aligned(16))) char sm[2 * 16384];  // K, V images (32 KiB)
+  char* Ki = sm;
+  char* Vi = sm + 16384;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
+  VarBlock w;
+  if (!var_block(cu, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
+  const int h = w.h, H = heads * AD;
+  const long W3 = 3L * H, q0 = (long)w.s0 + (long)w.blk * BLK;
+  if (w.blk == 0 && w.b == B - 1) zero_rows(dqkv, W3, h * AD, (long)w.s0 + w.len, T, tid);
+  const int qlive = min(BLK, w.len - w.blk * BLK), nkb = (w.len + BLK - 1) / BLK;
+  const int qb = wave * 32;
+  const bool wlive = qb < qlive;
+  short8 qreg[2][2] = {}, greg[2][2] = {};
+  float lq[2] = {0.f, 0.f}, Dv[2] = {0.f, 0.f};
+  bool qok[2] = {false, false};
+  if (wlive) {
+#pragma unroll
+    for (int qt = 0; qt < 2; qt++) {
+      const int row = qb + 16 * qt + fr;
+      qok[qt] = row < qlive;
+#pragma unroll
+      for (int ks = 0; ks < 2; ks++) {
+        const int c = h * AD + ks * 32 + fq * 8;
+        qreg[qt][ks] = row_operand<true>(qkv + (q0 + row) * W3 + c, qok[qt], bqkv + c, qscale);
+        greg[qt][ks] = row_operand<false>(dout + (q0 + row) * H + c, qok[qt], nullptr, 1.f);
+      }
+      if (qok[qt]) {
+        lq[qt] = lse[(long)h * T + q0 + row] * kLog2e;
+        Dv[qt] = Dq[(long)h * T + q0 + row];
+      }
+    }
+  }
+  floatx4 dqT[4][2];
+#pragma unroll
+  for (int dt = 0; dt < 4; dt++) dqT[dt][0] = dqT[dt][1] = floatx4{0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < nkb; j++) {
+    const int klive = min(BLK, w.len - j * BLK);
+    if (j > 0) __syncthreads();  // every wave is done with key block j-1
+    {
+      const int col[2] = {H + h * AD, 2 * H + h * AD};
+      const bool tf[2] = {true, true};
+      const float sc[2] = {1.f, 1.f};
+      char* const img[2] = {Ki, Vi};
+      const bf16_t* const src[2] = {qkv, qkv};
+      const long ld[2] = {W3, W3};
+      tail_images<2>(src, ld, (long)w.s0 + (long)j * BLK, col, bqkv, tf, sc, klive, img, tid);
+    }
+    __syncthreads();
+    if (!wlive) continue;
+    // one 32-key slice at a time (key tiles 2c, 2c + 1: a dropout hash pair and one dQ k-step), so
+    // only 2 x 2 score tiles are live.  s / dp[u][qt][r]: (q = qb + 16qt + fr, key = 32c + 16u + 4fq + r),
+    // dP(q, key) = dO[q]·V[key]
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      if (c * 32 >= klive) break;
+      floatx4 s[2][2], dp[2][2];
+#pragma unroll
+      for (int u = 0; u < 2; u++) {
+        s[u][0] = s[u][1] = dp[u][0] = dp[u][1] = floatx4{0.f, 0.f, 0.f, 0.f};
+        if (c * 32 + u * 16 < klive) {
+#pragma unroll
+          for (int ks = 0; ks < 2; ks++) {
+            const short8 ak = rd_row<64>(Ki, c * 32 + u * 16 + fr, ks * 32 + fq * 8);
+            const short8 av = rd_row<64>(Vi, c * 32 + u * 16 + fr, ks * 32 + fq * 8);
+#pragma unroll
+            for (int qt = 0; qt < 2; qt++) {
+              s[u][qt] = mma(ak, qreg[qt][ks], s[u][qt]);
+              dp[u][qt] = mma(av, greg[qt][ks], dp[u][qt]);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int qt = 0; qt < 2; qt++) {
+        const uint64_t row = (uint64_t)h * T + (uint64_t)(q0 + qb + qt * 16 + fr);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int key = c * 32 + 4 * fq + r;
+          const uint32_t hh = thresh ? attn_pair_hash(seed, row, max_seqlen, j * BLK + key) : 0u;
+#pragma unroll
+          for (int u = 0; u < 2; u++) {
+            const bool ok = qok[qt] && key + 16 * u < klive;  // else P = 0, whatever lse holds
+            const float p = ok ? __builtin_amdgcn_exp2f(fmaf(s[u][qt][r], kLog2e, -lq[qt])) : 0.f;
+            float g = dp[u][qt][r];
+            if (thresh) g = (u ? keep_hi(hh, thresh) : keep_lo(hh, thresh)) ? g * dscale : 0.f;
+            s[u][qt][r] = p * (g - Dv[qt]);  // dS
+          }
+        }
+      }
+      const int ra = 32 * c + 4 * fq, rb = ra + 16;
+      short8 ktr[4];
+#pragma unroll
+      for (int dt = 0; dt < 4; dt++) ktr[dt] = rd_tr2<64>(Ki, ra, rb, dt * 16, lane);
+#pragma unroll
+      for (int qt = 0; qt < 2; qt++) {
+        const short8 bs = pack_pair(s[0][qt], s[1][qt]);
+#pragma unroll
+        for (int dt = 0; dt < 4; dt++) dqT[dt][qt] = mma(ktr[dt], bs, dqT[dt][qt]);
+      }
+    }
+  }
+  __syncthreads();  // the K image becomes the output stage
+  if (!wlive) return;
+  char* st = sm + wave * 4096;
+  stage_tile(st, dqT, qscale, fr, fq);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  store_tile_rows(st, dqkv, q0 + qb, W3, h * AD, qlive - qb, dbqkv, lane);
+}
+
 // t16 = round(p·2^16) (0: no dropout) and the keep scale 2^16 / (2^16 − t16)
 uint32_t attn_drop_t16(float p) {
   if (!(p > 0.f)) return 0u;
@@ -1240,5 +1795,44 @@ KFA_API int kfa_attn_bwd(const void* qkv, const float* bqkv, const float* key_bi
                      (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, heads, S, qscale, th, ds, (uint64_t)seed);
   hipLaunchKernelGGL(attn_bwd_q_long_kernel, grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, key_bias, lse, work,
                      (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, heads, S, qscale, th, ds, (uint64_t)seed);
+  return kfa_status();
+}
+
+// Packed batches (see attn_varlen_fwd_kernel): qkv [T, 3·heads·64], cu int32 [B + 1] on the device
+// (the caller validates its host copy: the entries cannot), ctx [T, heads·64], lse [heads, T].
+// The grid comes from max_seqlen alone: no device-to-host sync.
+static bool attn_varlen_args_ok(int B, int T, int max_seqlen, int heads, int d) {
+  if (B <= 0 || T <= 0 || heads <= 0 || d != AD || max_seqlen < 1 || max_seqlen > 8192) return false;
+  return (long)B * heads * ((max_seqlen + BLK - 1) / BLK) < (1L << 31);
+}
+
+KFA_API int kfa_attn_varlen_fwd(const void* qkv, const float* bqkv, const int* cu, void* out, float* lse, int B, int T,
+                                int max_seqlen, int heads, int d, float qscale, float p, unsigned long long seed,
+                                hipStream_t st) {
+  if (!qkv || !bqkv || !cu || !out || !lse || !attn_varlen_args_ok(B, T, max_seqlen, heads, d)) return -1;
+  const uint32_t th = attn_drop_t16(p);
+  const dim3 grid((unsigned)((long)B * heads * ((max_seqlen + BLK - 1) / BLK)));
+  hipLaunchKernelGGL(attn_varlen_fwd_kernel, grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu, (bf16_t*)out, lse, B,
+                     T, heads, max_seqlen, qscale, th, attn_drop_scale(th), (uint64_t)seed);
+  return kfa_status();
+}
+
+// dqkv [T, 3H] (owned rows overwritten, unowned rows zeroed); dbqkv [3H] fp32 += bias gradient
+// (nullable); work: heads·T floats (D = rowsum(dO∘O) of every owned row)
+KFA_API int kfa_attn_varlen_bwd(const void* qkv, const float* bqkv, const int* cu, const void* out, const float* lse,
+                                const void* dout, void* dqkv, float* dbqkv, int B, int T, int max_seqlen, int heads,
+                                int d, float qscale, float p, unsigned long long seed, float* work, hipStream_t st) {
+  if (!qkv || !bqkv || !cu || !out || !lse || !dout || !dqkv || !attn_varlen_args_ok(B, T, max_seqlen, heads, d))
+    return -1;
+  if (!work) return -3;
+  const uint32_t th = attn_drop_t16(p);
+  const float ds = attn_drop_scale(th);
+  hipLaunchKernelGGL(attn_varlen_rowdot_kernel, dim3((unsigned)(((long)T * heads + 255) / 256)), dim3(256), 0, st,
+                     (const bf16_t*)dout, (const bf16_t*)out, cu, work, B, T, heads);
+  const dim3 grid((unsigned)((long)B * heads * ((max_seqlen + BLK - 1) / BLK)));
+  hipLaunchKernelGGL(attn_varlen_bwd_kv_kernel, grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu, lse, work,
+                     (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th, ds, (uint64_t)seed);
+  hipLaunchKernelGGL(attn_varlen_bwd_q_kernel, grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu, lse, work,
+                     (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th, ds, (uint64_t)seed);
   return kfa_status();
 }

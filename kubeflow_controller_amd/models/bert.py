@@ -192,6 +192,58 @@ class BertForPreTraining(nn.Module):
         nsp = classifier_xent(pooled.contiguous(), self.nsp_w, self.nsp_b, nsp_labels)  # fused 2-way head + loss
         return mlm + nsp
 
+    def forward_packed(self, input_ids, token_type_ids, position_ids, seqs, mlm_positions, mlm_labels, nsp_labels):
+        """The loss of :meth:`forward` on a packed batch (:func:`pack_batch`): flat [rows] ids /
+        types / positions, ``seqs`` the :class:`~kubeflow_controller_amd.ops.transformer.PackedSeqs`
+        table, ``mlm_positions`` packed row indices; the [CLS] rows are ``cu[:-1]``.  Every op but
+        attention is row-wise, so only attention (the varlen kernels) sees the table; no pad
+        row is computed except the unowned ones up to the row budget."""
+        cfg = self.cfg
+        H = cfg.hidden
+        if seqs.max_seqlen > cfg.max_position:
+            raise ValueError(f"forward_packed: max_seqlen {seqs.max_seqlen} exceeds max_position {cfg.max_position}")
+        seqs.validate(input_ids.numel())
+        if not input_ids.is_cuda:  # plain PyTorch fp32, no dropout
+            f = lambda t: t.float()  # noqa: E731
+            e = f(self.word_emb)[input_ids] + f(self.pos_emb)[position_ids] + f(self.type_emb)[token_type_ids]
+            h = F.layer_norm(e, (H,), f(self.emb_ln_g), f(self.emb_ln_b), cfg.ln_eps)
+            lcfg = (seqs.B, seqs.max_seqlen, cfg.heads, 0.0, 0.0, 0, cfg.ln_eps, None, None, seqs)
+            for layer in self.layers:
+                h = T.encoder_layer_reference(h, None, lcfg, *layer.params())
+            hm = h.index_select(0, mlm_positions.reshape(-1))
+            t = F.gelu(hm @ f(self.mlm_w).t() + f(self.mlm_b))
+            t = F.layer_norm(t, (H,), f(self.mlm_ln_g), f(self.mlm_ln_b), cfg.ln_eps)
+            mlm = F.cross_entropy(t @ f(self.word_emb).t() + f(self.dec_b), mlm_labels.reshape(-1))
+            pooled = torch.tanh(h.index_select(0, seqs.cu_host[:-1].long()) @ f(self.pool_w).t() + f(self.pool_b))
+            return mlm + F.cross_entropy(pooled @ f(self.nsp_w).t() + f(self.nsp_b), nsp_labels)
+        ph = cfg.hidden_dropout if self.training else 0.0
+        pa = cfg.attn_dropout if self.training else 0.0
+        step_seed = T.mix_seed(self.seed, self._step)
+        if self.training:
+            self._step += 1
+        e = T.embedding_sum([self.word_emb, self.pos_emb, self.type_emb],
+                            [input_ids.reshape(-1), position_ids.reshape(-1), token_type_ids.reshape(-1)])
+        h = T.layer_norm(e, self.emb_ln_g, self.emb_ln_b, cfg.ln_eps)
+        if ph > 0:
+            h = T.dense_dropout(h, ph, T.mix_seed(step_seed, 999))
+        join_in = None
+        for i, layer in enumerate(self.layers):
+            join_out = T.ResidualJoin() if (self.training and i + 1 < len(self.layers)) else None
+            lcfg = (seqs.B, seqs.max_seqlen, cfg.heads, ph, pa, T.s64(T.mix_seed(step_seed, i)), cfg.ln_eps, join_in,
+                    join_out, seqs)
+            h = T.EncoderLayerFn.apply(h, None, lcfg, *layer.params())
+            join_in = join_out
+        pos = mlm_positions.reshape(-1)
+        rows = torch.cat([pos.to(torch.int64), seqs.cu_dev[:-1].to(torch.int64)])
+        g = h.index_select(0, rows)
+        hm, hc = g[:pos.numel()], g[pos.numel():]
+        t = T.dense(hm, self.mlm_w, self.mlm_b, "gelu")
+        t = T.layer_norm(t, self.mlm_ln_g, self.mlm_ln_b, cfg.ln_eps)
+        mlm = T.decoder_xent(t, self.word_emb, self.dec_b, mlm_labels.reshape(-1))
+        pooled = T.dense(hc, self.pool_w, self.pool_b, "tanh")
+        nsp = classifier_xent(pooled.contiguous(), self.nsp_w, self.nsp_b, nsp_labels)
+        return mlm + nsp
+
     def forward_reference(self, input_ids, token_type_ids, attention_mask, mlm_positions, mlm_labels, nsp_labels):
         """Plain PyTorch fp32, no dropout (CPU replicas + numerics reference)."""
         cfg = self.cfg
@@ -215,6 +267,8 @@ class BertForPreTraining(nn.Module):
 
 
 def bert_loss(model, *batch):
+    if len(batch) == 7 and isinstance(batch[3], T.PackedSeqs):  # pack_batch / synthetic_packed_mlm_batch
+        return model.forward_packed(*batch)
     return model(*batch)
 
 
@@ -233,6 +287,71 @@ def synthetic_mlm_batch(cfg: BertConfig, batch: int, seq_len: int, generator=Non
     nsp = torch.randint(0, 2, (B,), generator=g)
     to = lambda t: t.to(device)  # noqa: E731
     return to(ids), to(tt), None, to(flat), to(labels), to(nsp)
+
+
+def pack_batch(input_ids, token_type_ids, attention_mask, mlm_positions, mlm_labels, nsp_labels, rows=None,
+               device=None):
+    """A padded [B, S] batch (0/1 ``attention_mask`` whose live tokens form a prefix of every
+    sequence; ``mlm_positions`` flat indices into [B·S]) as the positional arguments of
+    :meth:`BertForPreTraining.forward_packed`: the live tokens back to back, padded with id 0
+    up to ``rows`` token rows when given.  Runs on the host; the result lives on ``device``
+    (default: where ``input_ids`` is)."""
+    device = torch.device(device) if device is not None else input_ids.device
+    ids, tt, mask = input_ids.cpu(), token_type_ids.cpu(), attention_mask.cpu().long()
+    B, S = ids.shape
+    lens = mask.sum(1)
+    if not torch.equal(mask, (torch.arange(S)[None, :] < lens[:, None]).long()):
+        raise ValueError("pack_batch: every sequence's live tokens must form a prefix (attention_mask 1..1 0..0)")
+    cu = torch.zeros(B + 1, dtype=torch.int64)
+    cu[1:] = lens.cumsum(0)
+    total = int(cu[-1])
+    rows = total if rows is None else int(rows)
+    live = mask.bool()
+    pad = (0, max(rows - total, 0))
+    flat_ids = F.pad(ids[live], pad)
+    flat_tt = F.pad(tt[live], pad)
+    pos_ids = F.pad(torch.arange(S).expand(B, S)[live], pad)
+    mp = mlm_positions.cpu().reshape(-1).long()
+    b, t = mp // S, mp % S
+    if bool((t >= lens[b]).any()):
+        raise ValueError("pack_batch: a masked position falls on padding")
+    seqs = T.PackedSeqs(cu, rows, int(lens.max()), device)  # refuses an empty sequence or total > rows
+    to = lambda x: x.to(device)  # noqa: E731
+    return to(flat_ids), to(flat_tt), to(pos_ids), seqs, to(cu[b] + t), to(mlm_labels), to(nsp_labels)
+
+
+def synthetic_packed_mlm_batch(cfg: BertConfig, rows: int, seq_len: int, min_len: int, generator=None, device="cpu"):
+    """A packed counterpart of :func:`synthetic_mlm_batch`: sequence lengths uniform in
+    [min_len, seq_len], added while they fit in ``rows`` token rows (the remainder stays
+    unowned), min(max_predictions, len) masked positions per sequence.  Returns the
+    positional args of forward_packed()."""
+    g = generator
+    if not 1 <= min_len <= seq_len <= rows:
+        raise ValueError(f"synthetic_packed_mlm_batch: need 1 <= min_len <= seq_len <= rows, got {min_len}, {seq_len}, {rows}")
+    lens = []
+    while True:
+        n = int(torch.randint(min_len, seq_len + 1, (1,), generator=g))
+        if sum(lens) + n > rows:
+            break
+        lens.append(n)
+    cu = torch.tensor([0] + lens).cumsum(0)
+    ids = torch.zeros(rows, dtype=torch.int64)
+    ids[:cu[-1]] = torch.randint(0, cfg.vocab_size, (int(cu[-1]),), generator=g)
+    tt = torch.zeros(rows, dtype=torch.int64)
+    pos_ids = torch.zeros(rows, dtype=torch.int64)
+    mlm = []
+    for i, n in enumerate(lens):
+        s0 = int(cu[i])
+        split = int(torch.randint(n // 4, max(n // 4 + 1, 3 * n // 4), (1,), generator=g))
+        tt[s0 + split:s0 + n] = 1
+        pos_ids[s0:s0 + n] = torch.arange(n)
+        mlm.append(s0 + torch.randperm(n, generator=g)[:min(cfg.max_predictions, n)].sort().values)
+    mlm = torch.cat(mlm)
+    labels = torch.randint(0, cfg.vocab_size, (mlm.numel(),), generator=g)
+    nsp = torch.randint(0, 2, (len(lens),), generator=g)
+    seqs = T.PackedSeqs(cu, rows, seq_len, device)
+    to = lambda t: t.to(device)  # noqa: E731
+    return to(ids), to(tt), to(pos_ids), seqs, to(mlm), to(labels), to(nsp)
 
 
 def flops_per_step(cfg: BertConfig, batch: int, seq_len: int) -> float:

@@ -60,6 +60,8 @@ _lib.register("kfa_attn_fwd", [P, P, P, P, P, I, I, I, I, Fl, Fl, U64, P, P])
 _lib.register("kfa_attn_bwd", [P, P, P, P, P, P, P, P, I, I, I, I, Fl, Fl, U64, P, P, P, P])
 _lib.register("kfa_attn_dbias_part_floats", [I, I], L)
 _lib.register("kfa_attn_mask_words", [I, I, I], _lib.L)
+_lib.register("kfa_attn_varlen_fwd", [P, P, P, P, P, I, I, I, I, I, Fl, Fl, U64, P])
+_lib.register("kfa_attn_varlen_bwd", [P, P, P, P, P, P, P, P, I, I, I, I, I, Fl, Fl, U64, P, P])
 
 # env KFA_FUSED_ATTN=0 falls back to the split kernels + batched library GEMMs
 FUSED_ATTN = os.environ.get("KFA_FUSED_ATTN", "1") != "0"
@@ -536,6 +538,140 @@ def attn_bwd(qkv, bqkv, key_bias, out, lse, dout, dbqkv, B, S, heads, p=0.0, see
     return dqkv
 
 
+# ----------------------------------------------------------------------------- packed (varlen) attention
+class PackedSeqs:
+    """Sequence table of a packed batch: ``B`` sequences back to back in ``rows`` token
+    rows, sequence ``i`` owning rows ``cu[i] .. cu[i+1]-1``; rows ``cu[B] .. rows-1`` are
+    unowned padding up to the fixed row budget (attention writes zeros there).
+
+    Built once per batch from a host int32 table.  The kernels trust the device copy
+    (a bad table is an out-of-bounds access), so the host copy is validated here and
+    again by the wrappers before every launch; it must not be modified afterwards.
+    ``cu_dev`` is uploaded with one non-blocking copy from the pinned ``cu_host``."""
+
+    MAX_LEN = 8192
+
+    def __init__(self, cu, rows: int, max_seqlen: Optional[int] = None, device=None):
+        cu = torch.as_tensor(cu, dtype=torch.int32, device="cpu").reshape(-1)
+        device = torch.device(device) if device is not None else torch.device("cpu")
+        if cu.numel() < 2:
+            raise ValueError("PackedSeqs: the table needs at least one sequence (B + 1 entries)")
+        self.rows = int(rows)
+        self.max_seqlen = int(max_seqlen) if max_seqlen is not None else int((cu[1:] - cu[:-1]).max())
+        self.cu_host = torch.empty(cu.numel(), dtype=torch.int32, pin_memory=device.type == "cuda")
+        self.cu_host.copy_(cu)
+        self.validate()
+        self.cu_dev = self.cu_host.to(device, non_blocking=True) if device.type == "cuda" else self.cu_host
+
+    @property
+    def B(self) -> int:
+        return self.cu_host.numel() - 1
+
+    @property
+    def tokens(self) -> int:
+        return int(self.cu_host[-1])
+
+    def validate(self, rows: Optional[int] = None) -> None:
+        """ValueError unless cu[0] = 0, the table is strictly increasing (no empty
+        sequence), cu[B] <= rows and every length <= max_seqlen <= 8192."""
+        cu = self.cu_host.numpy()
+        if rows is not None and int(rows) != self.rows:
+            raise ValueError(f"PackedSeqs: built for {self.rows} rows, used with {rows}")
+        if int(cu[0]) != 0:
+            raise ValueError("PackedSeqs: cu_seqlens[0] must be 0")
+        lens = cu[1:].astype("int64") - cu[:-1].astype("int64")
+        if (lens <= 0).any():
+            raise ValueError("PackedSeqs: cu_seqlens must be strictly increasing (no empty sequence)")
+        if int(cu[-1]) > self.rows:
+            raise ValueError(f"PackedSeqs: cu_seqlens[B] = {int(cu[-1])} exceeds the {self.rows} rows")
+        if not 1 <= self.max_seqlen <= self.MAX_LEN:
+            raise ValueError(f"PackedSeqs: max_seqlen {self.max_seqlen} outside 1..{self.MAX_LEN}")
+        if int(lens.max()) > self.max_seqlen:
+            raise ValueError(f"PackedSeqs: a sequence of {int(lens.max())} tokens exceeds max_seqlen {self.max_seqlen}")
+
+
+def _varlen_check(name, qkv, bqkv, seqs, heads):
+    if not isinstance(seqs, PackedSeqs):
+        raise ValueError(f"{name}: seqs must be a PackedSeqs")
+    if qkv.dim() != 2 or qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
+        raise ValueError(f"{name}: qkv must be a contiguous bf16 [T, 3H] tensor")
+    T_, W3 = qkv.shape
+    if heads <= 0 or W3 % (3 * heads) or W3 // (3 * heads) != 64:
+        raise ValueError(f"{name}: head dim must be 64 (qkv {tuple(qkv.shape)}, heads={heads})")
+    seqs.validate(T_)
+    if not qkv.is_cuda or seqs.cu_dev.device != qkv.device:
+        raise ValueError(f"{name}: qkv and the sequence table must be on the same GPU "
+                         "(the CPU path is attention_varlen_reference)")
+    if bqkv is None:
+        return _zeros_f32(W3, qkv.device)
+    if bqkv.dtype != torch.float32 or bqkv.numel() != W3 or not bqkv.is_contiguous() or bqkv.device != qkv.device:
+        raise ValueError(f"{name}: bqkv must be a contiguous fp32 [3H] vector")
+    return bqkv
+
+
+def attn_varlen_fwd(qkv, bqkv, seqs: PackedSeqs, heads, p=0.0, seed=0):
+    """(ctx [T, H], lse [heads, T]) of per-sequence softmax((q+b)(k+b)ᵀ/√d)·(v+b) over the
+    packed batch ``seqs`` (``csrc/kernels/attention.hip``: attn_varlen_fwd_kernel); the
+    unowned rows of ctx are zero.  Dropout: hash row ``h·T + token row``, key index
+    within the sequence (attn_pair_hash with S = max_seqlen)."""
+    bqkv = _varlen_check("attn_varlen_fwd", qkv, bqkv, seqs, heads)
+    T_, W3 = qkv.shape
+    H = W3 // 3
+    out = torch.empty(T_, H, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(heads, T_, dtype=torch.float32, device=qkv.device)
+    _lib.call("kfa_attn_varlen_fwd", _lib.ptr(qkv), _lib.ptr(bqkv), _lib.ptr(seqs.cu_dev), _lib.ptr(out),
+              _lib.ptr(lse), seqs.B, T_, seqs.max_seqlen, heads, 64, 1.0 / math.sqrt(64), float(p), hash_key(seed),
+              _lib.stream())
+    return out, lse
+
+
+def attn_varlen_bwd(qkv, bqkv, seqs: PackedSeqs, out, lse, dout, dbqkv, heads, p=0.0, seed=0):
+    """dqkv [T, 3H] of :func:`attn_varlen_fwd` (``out``, ``lse``: its outputs; unowned rows
+    zero); the bias gradient is added into ``dbqkv`` (fp32 [3H], nullable)."""
+    bqkv = _varlen_check("attn_varlen_bwd", qkv, bqkv, seqs, heads)
+    T_, W3 = qkv.shape
+    H = W3 // 3
+    dout = dout.contiguous()
+    if tuple(dout.shape) != (T_, H) or dout.dtype != qkv.dtype or dout.device != qkv.device:
+        raise ValueError("attn_varlen_bwd: dout must be bf16 [T, H]")
+    if tuple(out.shape) != (T_, H) or out.dtype != qkv.dtype or not out.is_contiguous() or out.device != qkv.device:
+        raise ValueError("attn_varlen_bwd: out must be the contiguous bf16 [T, H] forward output")
+    if (tuple(lse.shape) != (heads, T_) or lse.dtype != torch.float32 or not lse.is_contiguous()
+            or lse.device != qkv.device):
+        raise ValueError("attn_varlen_bwd: lse must be the contiguous fp32 [heads, T] forward output")
+    if dbqkv is not None and (dbqkv.dtype != torch.float32 or dbqkv.numel() != W3 or not dbqkv.is_contiguous()
+                              or dbqkv.device != qkv.device):
+        raise ValueError("attn_varlen_bwd: dbqkv must be a contiguous fp32 [3H] vector")
+    dqkv = torch.empty_like(qkv)
+    work = _lib.workspace(heads * T_ * 4, qkv.device, "attn_rowdot")  # D = rowsum(dO∘O) [heads, T]
+    _lib.call("kfa_attn_varlen_bwd", _lib.ptr(qkv), _lib.ptr(bqkv), _lib.ptr(seqs.cu_dev), _lib.ptr(out),
+              _lib.ptr(lse), _lib.ptr(dout), _lib.ptr(dqkv), _lib.ptr(dbqkv), seqs.B, T_, seqs.max_seqlen, heads, 64,
+              1.0 / math.sqrt(64), float(p), hash_key(seed), _lib.ptr(work), _lib.stream())
+    return dqkv
+
+
+def attention_varlen_reference(qkv, bqkv, seqs: PackedSeqs, heads, keep=None, keep_scale=1.0):
+    """Plain fp32 PyTorch: ctx [T, H] of the packed batch, one sequence at a time; the
+    unowned rows are zero.  ``keep`` (optional): per sequence a [heads, len, len] 0/1
+    dropout keep mask, kept probabilities scaled by ``keep_scale``."""
+    T_, W3 = qkv.shape
+    H = W3 // 3
+    d = H // heads
+    x = qkv.float()
+    if bqkv is not None:
+        x = x + bqkv.float()
+    cu = seqs.cu_host.tolist()
+    parts = []
+    for i in range(len(cu) - 1):
+        q, k, v = x[cu[i]:cu[i + 1]].view(-1, 3, heads, d).permute(1, 2, 0, 3)   # [heads, len, d]
+        pr = torch.softmax((q @ k.transpose(-1, -2)) / math.sqrt(d), -1)
+        if keep is not None:
+            pr = pr * keep[i] * keep_scale
+        parts.append((pr @ v).permute(1, 0, 2).reshape(-1, H))
+    parts.append(x.new_zeros(T_ - cu[-1], H))
+    return torch.cat(parts)
+
+
 def _ffn_up(h, w, b):
     """FFN-up forward ``(gelu(h @ w.T + b), z, z_has_bias)``: per shape the fastest of
     the GEMM (hipBLASLt or an own persistent variant) + the bias/GELU pass, and the own
@@ -595,9 +731,12 @@ class EncoderLayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, key_bias, cfg, wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2):
         # cfg[7:9] (optional): ResidualJoin of this layer's input (deposited into by
-        # the backward) and of its output (taken from by the backward)
+        # the backward) and of its output (taken from by the backward); cfg[9] (optional):
+        # the PackedSeqs of a packed batch — x is then [rows, H], attention runs per
+        # sequence through the varlen kernels (B and S are not used) and key_bias is None
         B, S, heads, ph, pa, seed, eps = cfg[:7]
         ctx.joins = (tuple(cfg[7:9]) + (None, None))[:2]
+        seqs = cfg[9] if len(cfg) > 9 else None
         _gemm.mark_weights_stale()  # the dgrad's cached weight transposes refresh at the next backward
         T, H = x.shape
         d = H // heads
@@ -611,9 +750,17 @@ class EncoderLayerFn(torch.autograd.Function):
         # persistent MFMA GEMM or hipBLASLt, whichever measured faster (ops/gemm.mm_auto)
         mm = (lambda a, w: _gemm.gemm_nt(a, w)[0]) if use_g else _gemm.mm_auto  # noqa: E731
         fused = fused_attention_ok(S, d)
+        if seqs is not None:
+            if key_bias is not None:
+                raise ValueError("EncoderLayerFn: a packed batch has no padded keys; key_bias must be None")
+            if d != 64:
+                raise ValueError(f"EncoderLayerFn: packed attention needs head dim 64, got {d}")
         # attention
         qkv = mm(x, wqkv)                                                 # [T, 3H]
-        if fused:
+        if seqs is not None:
+            ctxr, lse = attn_varlen_fwd(qkv, bqkv, seqs, heads, pa, s_attn)
+            att = (qkv, lse)
+        elif fused:
             ctxr, lse, amask = attn_fwd(qkv, bqkv, key_bias, B, S, heads, pa, s_attn, want_mask=True) if ATTN_MASK \
                 else attn_fwd(qkv, bqkv, key_bias, B, S, heads, pa, s_attn) + (None,)
             att = (qkv, lse, amask)
@@ -648,6 +795,7 @@ class EncoderLayerFn(torch.autograd.Function):
         ctx.params = (wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2)
         ctx.cfg = (B, S, heads, ph, pa, (s_attn, s_h1, s_h2), qscale, use_g, use_f, fused, z_bias)
         ctx.key_bias = key_bias
+        ctx.seqs = seqs
         return h2
 
     @staticmethod
@@ -687,7 +835,12 @@ class EncoderLayerFn(torch.autograd.Function):
         dctxr = _gemm.gemm_nt(dao, _gemm.transpose(wo))[0] if use_g else _gemm.dgrad_auto(dao, wo)
         res_shared = dao is dx_res  # no hidden dropout: one tensor, also the side stream's wgrad operand
         del dao
-        if fused:
+        if ctx.seqs is not None:
+            qkv, lse = att
+            dqkv = attn_varlen_bwd(qkv, bqkv, ctx.seqs, ctxr, lse, dctxr, None, heads, pa, s_attn)
+            colsum_(dqkv, G(bqkv))  # as the fused path: one column-sum pass over the still-cached dqkv
+            del dctxr
+        elif fused:
             qkv, lse, amask = att
             # QKV-bias gradient: a column-sum pass over dqkv (it is still in the Infinity
             # Cache); KFA_ATTN_DBIAS=1: the kernel's per-(sequence, wave) column sums of the
@@ -732,19 +885,26 @@ class EncoderLayerFn(torch.autograd.Function):
 
 
 def encoder_layer_reference(x, key_bias, cfg, wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2):
-    """Plain PyTorch fp32 reference (no dropout)."""
-    B, S, heads, _, _, _, eps = cfg
+    """Plain PyTorch fp32 reference (no dropout); cfg[9] (optional): the PackedSeqs of a
+    packed batch (x [rows, H], attention per sequence, no key_bias)."""
+    B, S, heads, _, _, _, eps = cfg[:7]
+    seqs = cfg[9] if len(cfg) > 9 else None
     T, H = x.shape
     d = H // heads
     f = lambda t: t.float()  # noqa: E731
     x = f(x)
     qkv = x @ f(wqkv).t() + f(bqkv)
-    q, k, v = qkv.view(B, S, 3, heads, d).permute(2, 0, 3, 1, 4)
-    sc = (q @ k.transpose(-1, -2)) / math.sqrt(d)
-    if key_bias is not None:
-        sc = sc + key_bias.view(B, 1, 1, S)
-    a = torch.softmax(sc, -1) @ v
-    a = a.permute(0, 2, 1, 3).reshape(T, H)
+    if seqs is not None:
+        if key_bias is not None:
+            raise ValueError("encoder_layer_reference: a packed batch takes no key_bias")
+        a = attention_varlen_reference(qkv, None, seqs, heads)
+    else:
+        q, k, v = qkv.view(B, S, 3, heads, d).permute(2, 0, 3, 1, 4)
+        sc = (q @ k.transpose(-1, -2)) / math.sqrt(d)
+        if key_bias is not None:
+            sc = sc + key_bias.view(B, 1, 1, S)
+        a = torch.softmax(sc, -1) @ v
+        a = a.permute(0, 2, 1, 3).reshape(T, H)
     h1 = F.layer_norm(a @ f(wo).t() + f(bo) + x, (H,), f(g1), f(be1), eps)
     ff = F.gelu(h1 @ f(w1).t() + f(b1)) @ f(w2).t() + f(b2)
     return F.layer_norm(ff + h1, (H,), f(g2), f(be2), eps)

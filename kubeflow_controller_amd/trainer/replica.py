@@ -203,7 +203,10 @@ def synthetic_batch(args, model, device, rank: int):
         y = torch.randint(0, 1000 if args.model == "resnet50" else 10, (B,), generator=g).to(device)
         return (x, y)
     if args.model.startswith("bert"):
-        from ..models.bert import synthetic_mlm_batch
+        from ..models.bert import synthetic_mlm_batch, synthetic_packed_mlm_batch
+        if args.pack_sequences:  # variable-length sequences packed into the same row budget, no pad rows
+            return synthetic_packed_mlm_batch(model.cfg, B * args.seq_len, args.seq_len,
+                                              min(args.min_seq_len, args.seq_len), g, device)
         return synthetic_mlm_batch(model.cfg, B, args.seq_len, g, device)
     if args.model.startswith("wide_deep"):
         from ..models.wide_deep import prepare_batch
@@ -533,6 +536,8 @@ def run_worker(spec: ClusterSpec, args) -> int:
     # step of more than GRAPH_AUTO_MS keeps eager launches (ResNet-50 at batch 256:
     # 21.8 ms eager, replay measured 0.5 % slower; the reference's MNIST: 0.2 ms).
     use_graph = args.graph == "on" or (args.graph == "auto" and world == 1 and device.type == "cuda")
+    if args.pack_sequences and args.model.startswith("bert"):
+        use_graph = False  # the packed batch carries a host sequence table that is checked before every launch
     cap_step = 1 if args.graph == "on" else 2
     if hasattr(data, "eval_batches"):  # image dataset: resident in HBM or staged through pinned buffers
         _place_images(data, device, rank, world, resumed // inc, bool(use_gpu and args.bf16))
@@ -646,6 +651,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--weight_decay", type=float, default=0.0)
     ap.add_argument("--hidden_units", type=int, default=100)
     ap.add_argument("--seq_len", type=int, default=128)
+    ap.add_argument("--pack_sequences", action="store_true",
+                    help="BERT: train on variable-length sequences (lengths uniform in [--min_seq_len, --seq_len]) "
+                         "packed into batch_size * seq_len token rows instead of a padded [batch_size, seq_len] batch")
+    ap.add_argument("--min_seq_len", type=int, default=16, help="shortest sequence of a --pack_sequences batch")
     ap.add_argument("--sync_replicas", action="store_true")
     ap.add_argument("--ps_mode", default="auto", choices=["auto", "async", "collective"],
                     help="async: PS tasks own variables + Adam (reference default); collective: RCCL "

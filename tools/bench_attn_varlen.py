@@ -1,0 +1,107 @@
+"""Packed (varlen) vs padded attention and BERT-base training step, sides alternated in one run.
+
+    python tools/bench_attn_varlen.py [--rounds 5] [--no-step]
+
+attention  one BERT-base layer (12 heads, dropout 0.1), 256 sequences with lengths uniform in
+           [16, 128]: fwd + bwd of the S = 128 kernels on the padded [256, 128] batch (key bias on
+           the pad keys) against the varlen kernels on the same sequences packed into sum(len) rows.
+step       one Engine step of BERT-base on synthetic_mlm_batch(256, 128) against
+           synthetic_packed_mlm_batch(rows = 256·128, lengths uniform in [16, 128]).
+Each round times every side once (events around 20 calls / 5 steps); prints per-side min and
+median over the rounds.
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from kubeflow_controller_amd.ops import transformer as T  # noqa: E402
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def alternate(sides, rounds, iters):
+    for fn in sides.values():  # warm-up: code objects, workspaces, the GEMM tuner's choices
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    t = {k: [] for k in sides}
+    for _ in range(rounds):
+        for k, fn in sides.items():
+            t[k].append(timed(fn, iters))
+    return {k: (min(v), statistics.median(v)) for k, v in t.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--no-step", action="store_true")
+    args = ap.parse_args()
+    d = torch.device("cuda")
+    g = torch.Generator().manual_seed(0)
+    torch.manual_seed(0)
+    B, S, h, p = 256, 128, 12, 0.1
+    H = h * 64
+    lens = torch.randint(16, S + 1, (B,), generator=g)
+    live = int(lens.sum())
+    cu = torch.cat([torch.zeros(1, dtype=torch.long), lens.cumsum(0)])
+    seqs = T.PackedSeqs(cu, live, S, d)
+    keep = (torch.arange(S)[None, :] < lens[:, None])
+    kb = ((~keep).float() * -10000.0).to(d).contiguous()
+    qkv_pad = torch.randn(B * S, 3 * H, device=d).to(torch.bfloat16)
+    qkv_pk = qkv_pad[keep.reshape(-1).to(d)].contiguous()
+    bqkv = torch.randn(3 * H, device=d) * 0.1
+    do_pad = torch.randn(B * S, H, device=d).to(torch.bfloat16)
+    do_pk = do_pad[keep.reshape(-1).to(d)].contiguous()
+
+    def padded():
+        out, lse = T.attn_fwd(qkv_pad, bqkv, kb, B, S, h, p, 7)
+        T.attn_bwd(qkv_pad, bqkv, kb, out, lse, do_pad, None, B, S, h, p, 7)
+
+    def packed():
+        out, lse = T.attn_varlen_fwd(qkv_pk, bqkv, seqs, h, p, 7)
+        T.attn_varlen_bwd(qkv_pk, bqkv, seqs, out, lse, do_pk, None, h, p, 7)
+
+    sides = {"padded fwd": lambda: T.attn_fwd(qkv_pad, bqkv, kb, B, S, h, p, 7),
+             "packed fwd": lambda: T.attn_varlen_fwd(qkv_pk, bqkv, seqs, h, p, 7),
+             "padded fwd+bwd": padded, "packed fwd+bwd": packed}
+    r = alternate(sides, args.rounds, 20)
+    print(f"attention: {B} sequences, lengths uniform in [16, {S}] (min {int(lens.min())}, max {int(lens.max())}), "
+          f"{live} live of {B * S} padded rows (f = {live / (B * S):.3f})")
+    for k, (lo, med) in r.items():
+        rows = live if k.startswith("packed") else B * S
+        print(f"  {k:15s} min {lo * 1e3:7.1f} us  median {med * 1e3:7.1f} us  ({lo * 1e6 / rows:6.2f} ns per row of its batch, "
+              f"{lo * 1e6 / live:6.2f} ns per live token)", flush=True)
+    if args.no_step:
+        return
+    from kubeflow_controller_amd.models.bert import (BertConfig, BertForPreTraining, bert_loss, synthetic_mlm_batch,
+                                                     synthetic_packed_mlm_batch)
+    from kubeflow_controller_amd.trainer.engine import DistInfo, Engine
+    cfg = BertConfig.base()
+    eng = Engine(BertForPreTraining(cfg), bert_loss, optimizer="adam", lr=1e-4, weight_decay=0.01,
+                 dist_info=DistInfo(device=d), channels_last=False)
+    pad_b = synthetic_mlm_batch(cfg, B, S, g, d)
+    pk_b = synthetic_packed_mlm_batch(cfg, B * S, S, 16, g, d)
+    r = alternate({"padded": lambda: eng.train_step(*pad_b), "packed": lambda: eng.train_step(*pk_b)}, args.rounds, 5)
+    nseq = {"padded": B, "packed": pk_b[3].B}
+    toks = {"padded": B * S, "packed": pk_b[3].tokens}
+    print(f"BERT-base step, {B * S} rows: padded {B} x {S} (every row live) vs packed {nseq['packed']} sequences "
+          f"({toks['packed']} live tokens, lengths uniform in [16, {S}])")
+    for k, (lo, med) in r.items():
+        print(f"  {k:7s} min {lo:7.2f} ms  median {med:7.2f} ms  {nseq[k] / lo * 1e3:8.0f} sequences/s  "
+              f"{toks[k] / lo * 1e3 / 1e6:6.3f} M live tokens/s", flush=True)
+
+
+if __name__ == "__main__":
+    main()
