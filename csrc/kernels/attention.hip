@@ -1673,6 +1673,530 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_varlen_bwd_q_kernel
   store_tile_rows(st, dqkv, q0 + qb, W3, h * AD, qlive - qb, dbqkv, lane);
 }
 
+// ============================================================================
+// Causal attention over the same packed layout: query i of a sequence sees keys
+// 0..i of that sequence.  Contracts (qkv, cu, out, lse, D, unowned rows, dropout
+// hash) are those of the varlen kernels above; attn_varlen_rowdot_kernel is shared.
+//
+// Triangular work, paired blocks.  With nbs = ceil(len / 128), query block i needs
+// key blocks 0..i (forward, dQ) and key block j needs query blocks j..nbs-1
+// (dK / dV).  A workgroup owns (sequence, head, pair p) and runs block p, then
+// block nbs-1-p (once, when the two are the same block): every workgroup of a
+// sequence streams nbs + 1 blocks, whatever order the hardware dispatches them in.
+// The grid is ceil(ceil(max_seqlen / 128) / 2)·B·heads; p >= ceil(nbs / 2) exits
+// before any barrier.  The two passes share the 32 KiB of images; the register
+// operands and accumulators of the second pass are set up after the first's stores.
+//
+// Blocks off the diagonal run the varlen step as it is: they are full blocks on the
+// key side (kend = 128), so no tail rule fires for keys, and the query tail rules of
+// the dK / dV step stay.  In the diagonal block a wave owns 32 rows, so everything
+// wave-uniform is the varlen tail rule with a per-wave bound, kend = min(live keys,
+// the wave's last query + 1): a 16-key score tile at or past kend issues no MFMA, a
+// 32-key P·V / dQ slice past it and a 32-query dK / dV step before the wave's first
+// key are skipped.  Only the tiles the diagonal crosses, behind one uniform branch,
+// select on key > query: the forward gives those pairs kMasked before the running
+// max, the backward kernels force their P to 0.  Dropout hashes are evaluated only in
+// slices / steps that hold a visible pair; a masked pair's P is 0 whatever it draws.
+// key > query ? masked : x, as a bit select on the sign of query − key (no compare mask per element)
+__device__ __forceinline__ float above_diag(int query, int key, float masked, float x) {
+  const uint32_t m = (uint32_t)((query - key) >> 31);  // all ones: key > query
+  return __uint_as_float((__float_as_uint(masked) & m) | (__float_as_uint(x) & ~m));
+}
+
+struct CausalPair {
+  int p, b, h, s0, len, nbs;
+};
+__device__ __forceinline__ bool causal_pair(const int* __restrict__ cu, int T, int heads, int max_seqlen,
+                                            CausalPair& w) {
+  const int np = ((max_seqlen + BLK - 1) / BLK + 1) / 2;
+  const int sh = blockIdx.x / np;
+  w.p = blockIdx.x - sh * np;
+  w.b = sh / heads;
+  w.h = sh - w.b * heads;
+  w.s0 = max(cu[w.b], 0);
+  w.len = min(cu[w.b + 1], T) - w.s0;  // a table the host validated; the clamps only keep a stale one in bounds
+  w.nbs = (w.len + BLK - 1) / BLK;
+  return 2 * w.p < w.nbs;
+}
+
+__global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_causal_fwd_kernel(const bf16_t* __restrict__ qkv,
+                                                                 const float* __restrict__ bqkv,
+                                                                 const int* __restrict__ cu, bf16_t* __restrict__ out,
+                                                                 float* __restrict__ lse, int B, int T, int heads,
+                                                                 int max_seqlen, float qscale, uint32_t thresh,
+                                                                 float dscale, uint64_t seed) {
+  __shared__ __attribute__((aligned(16))) char sm[2 * 16384];  // K, V images (32 KiB), both passes
+  char* Ki = sm;
+  char* Vi = sm + 16384;
+  const int tid0 = threadIdx.x;
+  CausalPair w;
+  if (!causal_pair(cu, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
+  const int h = w.h, H = heads * AD;
+  const long W3 = 3L * H;
+  if (w.p == 0 && w.b == B - 1) zero_rows(out, H, h * AD, (long)w.s0 + w.len, T, tid0);
+  const int npass = w.nbs - 1 - w.p != w.p ? 2 : 1;
+#pragma unroll 1
+  for (int pass = 0; pass < npass; pass++) {
+    // the lane's indices are formed again in each pass: held across both, the addresses derived
+    // from them would not fit the register budget
+    int tid = tid0;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
+    const int qb = wave * 32;
+    const int blk = pass ? w.nbs - 1 - w.p : w.p;
+    const long q0 = (long)w.s0 + (long)blk * BLK;
+    const int qlive = min(BLK, w.len - blk * BLK);
+    const bool wlive = qb < qlive;  // else: this wave's queries do not exist
+    short8 qreg[2][2] = {};
+    if (wlive) {
+#pragma unroll
+      for (int qt = 0; qt < 2; qt++)
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+          const int row = qb + 16 * qt + fr, c = h * AD + ks * 32 + fq * 8;
+          qreg[qt][ks] = row_operand<true>(qkv + (q0 + row) * W3 + c, row < qlive, bqkv + c, qscale * kLog2e);
+        }
+    }
+    float m[2] = {kMasked, kMasked}, l[2] = {0.f, 0.f};
+    floatx4 o[4][2];
+#pragma unroll
+    for (int dt = 0; dt < 4; dt++) o[dt][0] = o[dt][1] = floatx4{0.f, 0.f, 0.f, 0.f};
+    const uint64_t hrow = (uint64_t)h * T + (uint64_t)(q0 + qb);
+    for (int j = 0; j <= blk; j++) {  // the loop bound is the mask below the diagonal
+      const int klive = min(BLK, w.len - j * BLK);  // BLK unless j == blk
+      if (j > 0 || pass > 0) __syncthreads();  // every wave is done with the images (or the O stage)
+      {
+        const int col[2] = {H + h * AD, 2 * H + h * AD};
+        const bool tf[2] = {true, true};
+        const float sc[2] = {1.f, 1.f};
+        char* const img[2] = {Ki, Vi};
+        const bf16_t* const src[2] = {qkv, qkv};
+        const long ld[2] = {W3, W3};
+        tail_images<2>(src, ld, (long)w.s0 + (long)j * BLK, col, bqkv, tf, sc, klive, img, tid);
+      }
+      __syncthreads();
+      if (!wlive) continue;
+      // keys of this block the wave's queries can see: all 128 below the diagonal; on it the wave's
+      // own tail, min(live keys, its last query + 1) — the varlen tail rule with a per-wave bound
+      const bool diag = j == blk;
+      const int kend = diag ? min(klive, qb + 32) : BLK;
+      // s[kt][qt][r] = score(q = qb + 16qt + fr, key = 16kt + 4fq + r); tiles past kend stay 0 until masked
+      floatx4 s[8][2];
+#pragma unroll
+      for (int kt = 0; kt < 8; kt++) {
+        s[kt][0] = s[kt][1] = floatx4{0.f, 0.f, 0.f, 0.f};
+        if (kt * 16 < kend) {
+#pragma unroll
+          for (int ks = 0; ks < 2; ks++) {
+            const short8 a = rd_row<64>(Ki, kt * 16 + fr, ks * 32 + fq * 8);
+            s[kt][0] = mma(a, qreg[0][ks], s[kt][0]);
+            s[kt][1] = mma(a, qreg[1][ks], s[kt][1]);
+          }
+        }
+      }
+      if (diag) {
+        // tiles the diagonal crosses or that lie above it: key > query is masked.  A live query's
+        // keys at or past klive are past the query too, so this is the tail rule as well.
+#pragma unroll
+        for (int kt = 0; kt < 8; kt++)
+          if (kt * 16 + 15 > qb) {
+#pragma unroll
+            for (int qt = 0; qt < 2; qt++)
+#pragma unroll
+              for (int r = 0; r < 4; r++)
+                s[kt][qt][r] = above_diag(qb + 16 * qt + fr, kt * 16 + 4 * fq + r, kMasked, s[kt][qt][r]);
+          }
+      }
+#pragma unroll
+      for (int qt = 0; qt < 2; qt++) {
+        float mx = kMasked;
+#pragma unroll
+        for (int kt = 0; kt < 8; kt++)
+#pragma unroll
+          for (int r = 0; r < 4; r++) mx = fmaxf(mx, s[kt][qt][r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        // finite, as in the varlen forward: key 0 of the sequence is visible to every query, and every
+        // query's first block is block 0 (below the diagonal whole, on it through key 0 <= query)
+        const float mn = fmaxf(m[qt], mx);
+        const float alpha = __builtin_amdgcn_exp2f(m[qt] - mn);
+        float sum = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < 8; kt++)
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const float e = __builtin_amdgcn_exp2f(s[kt][qt][r] - mn);
+            s[kt][qt][r] = e;
+            sum += e;
+          }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        l[qt] = l[qt] * alpha + sum;
+        m[qt] = mn;
+#pragma unroll
+        for (int dt = 0; dt < 4; dt++)
+#pragma unroll
+          for (int r = 0; r < 4; r++) o[dt][qt][r] *= alpha;
+        if (thresh) {
+          const uint64_t row = hrow + (uint64_t)(qt * 16 + fr);
+#pragma unroll
+          for (int kp = 0; kp < 4; kp++)
+            if (kp * 32 < kend) {  // a slice past kend holds P = 0 only
+#pragma unroll
+              for (int r = 0; r < 4; r++) {
+                const uint32_t hh = attn_pair_hash(seed, row, max_seqlen, j * BLK + 32 * kp + 4 * fq + r);
+                s[2 * kp][qt][r] = keep_lo(hh, thresh) ? s[2 * kp][qt][r] * dscale : 0.f;
+                s[2 * kp + 1][qt][r] = keep_hi(hh, thresh) ? s[2 * kp + 1][qt][r] * dscale : 0.f;
+              }
+            }
+        }
+      }
+      // Oᵀ += Vᵀ·Pdᵀ from registers, as attn_varlen_fwd_kernel
+#pragma unroll
+      for (int ks = 0; ks < 4; ks++)
+        if (ks * 32 < kend) {
+          const short8 b0 = pack_pair(s[2 * ks][0], s[2 * ks + 1][0]);
+          const short8 b1 = pack_pair(s[2 * ks][1], s[2 * ks + 1][1]);
+          const int ra = 32 * ks + 4 * fq;
+#pragma unroll
+          for (int dt = 0; dt < 4; dt++) {
+            const short8 a = rd_tr2<64>(Vi, ra, ra + 16, dt * 16, lane);
+            o[dt][0] = mma(a, b0, o[dt][0]);
+            o[dt][1] = mma(a, b1, o[dt][1]);
+          }
+        }
+    }
+    __syncthreads();  // every wave is done with the K image: it becomes the O stage
+    if (!wlive) continue;
+#pragma unroll
+    for (int qt = 0; qt < 2; qt++) {
+      const int q = qb + qt * 16 + fr;
+      const float inv = 1.f / l[qt];
+      if (fq == 0 && q < qlive) lse[(long)h * T + q0 + q] = (m[qt] + __log2f(l[qt])) * kLn2;  // natural-log units
+#pragma unroll
+      for (int dt = 0; dt < 4; dt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) o[dt][qt][r] *= inv;
+    }
+    char* st = Ki + wave * 4096;
+    stage_tile(st, o, 1.f, fr, fq);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    store_tile_rows(st, out, q0 + qb, H, h * AD, qlive - qb, nullptr, lane);
+  }
+}
+
+// key-owner dK / dV: key block blk of a pair streams the query blocks blk..nbs-1 (Q, dO images)
+__global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_causal_bwd_kv_kernel(
+    const bf16_t* __restrict__ qkv, const float* __restrict__ bqkv, const int* __restrict__ cu,
+    const float* __restrict__ lse, const float* __restrict__ Dq, const bf16_t* __restrict__ dout,
+    bf16_t* __restrict__ dqkv, float* __restrict__ dbqkv, int B, int T, int heads, int max_seqlen, float qscale,
+    uint32_t thresh, float dscale, uint64_t seed) {
+  __shared__ __attribute__((aligned(16))) char sm[2 * 16384];  // Q, dO images (32 KiB), both passes
+  char* Qi = sm;
+  char* Gi = sm + 16384;
+  const int tid0 = threadIdx.x;
+  CausalPair w;
+  if (!causal_pair(cu, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
+  const int h = w.h, H = heads * AD;
+  const long W3 = 3L * H;
+  if (w.p == 0 && w.b == B - 1) {
+    zero_rows(dqkv, W3, H + h * AD, (long)w.s0 + w.len, T, tid0);
+    zero_rows(dqkv, W3, 2 * H + h * AD, (long)w.s0 + w.len, T, tid0);
+  }
+  const int npass = w.nbs - 1 - w.p != w.p ? 2 : 1;
+#pragma unroll 1
+  for (int pass = 0; pass < npass; pass++) {
+    // the lane's indices are formed again in each pass: held across both, the addresses derived
+    // from them would not fit the register budget
+    int tid = tid0;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
+    const int kw = wave * 32;
+    const int blk = pass ? w.nbs - 1 - w.p : w.p;
+    const long k0 = (long)w.s0 + (long)blk * BLK;
+    const int klive = min(BLK, w.len - blk * BLK);
+    const bool wlive = kw < klive;  // else: this wave's keys do not exist
+    short8 kreg[2][2] = {}, vreg[2][2] = {};
+    bool keyok[2] = {false, false};
+    if (wlive) {
+#pragma unroll
+      for (int kt = 0; kt < 2; kt++) {
+        const int row = kw + 16 * kt + fr;
+        keyok[kt] = row < klive;
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+          const int c = h * AD + ks * 32 + fq * 8;
+          kreg[kt][ks] = row_operand<true>(qkv + (k0 + row) * W3 + H + c, keyok[kt], bqkv + H + c, 1.f);
+          vreg[kt][ks] = row_operand<true>(qkv + (k0 + row) * W3 + 2 * H + c, keyok[kt], bqkv + 2 * H + c, 1.f);
+        }
+      }
+    }
+    floatx4 dvT[4][2], dkT[4][2];
+#pragma unroll
+    for (int dt = 0; dt < 4; dt++) dvT[dt][0] = dvT[dt][1] = dkT[dt][0] = dkT[dt][1] = floatx4{0.f, 0.f, 0.f, 0.f};
+    for (int i = blk; i < w.nbs; i++) {  // the loop bound is the mask: query blocks before blk see no key here
+      const int qlive = min(BLK, w.len - i * BLK);
+      const long qrow0 = (long)w.s0 + (long)i * BLK;
+      if (i > blk || pass > 0) __syncthreads();  // every wave is done with the images (or the output stage)
+      {
+        const int col[2] = {h * AD, h * AD};
+        const bool tf[2] = {true, false};
+        const float sc[2] = {qscale, 1.f};
+        char* const img[2] = {Qi, Gi};
+        const bf16_t* const src[2] = {qkv, dout};
+        const long ld[2] = {W3, (long)H};
+        tail_images<2>(src, ld, qrow0, col, bqkv, tf, sc, qlive, img, tid);
+      }
+      // lse·log2(e) and D of queries lane and lane + 64 of the block (0 where there is no query)
+      float lq2[2] = {0.f, 0.f}, dd2[2] = {0.f, 0.f};
+#pragma unroll
+      for (int u = 0; u < 2; u++)
+        if (wlive && lane + 64 * u < qlive) {
+          lq2[u] = lse[(long)h * T + qrow0 + lane + 64 * u] * kLog2e;
+          dd2[u] = Dq[(long)h * T + qrow0 + lane + 64 * u];
+        }
+      __syncthreads();
+      if (!wlive) continue;
+      const uint64_t hrow = (uint64_t)h * T + (uint64_t)qrow0;
+      // on the diagonal the 32-query steps before the wave's keys (32j + 31 < kw) see none of them
+      const bool diag = i == blk;
+      for (int j = diag ? wave : 0; j < 4 && 32 * j < qlive; j++) {
+        const float lqs = j >> 1 ? lq2[1] : lq2[0], dds = j >> 1 ? dd2[1] : dd2[0];
+        // s / dp[qt][kt][r]: (q = 32j + 16qt + 4fq + r, key = kw + 16kt + fr)
+        floatx4 s[2][2], dp[2][2];
+#pragma unroll
+        for (int qt = 0; qt < 2; qt++) s[qt][0] = s[qt][1] = dp[qt][0] = dp[qt][1] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++)
+#pragma unroll
+          for (int qt = 0; qt < 2; qt++) {
+            const short8 aq = rd_row<64>(Qi, 32 * j + 16 * qt + fr, ks * 32 + fq * 8);
+            const short8 ag = rd_row<64>(Gi, 32 * j + 16 * qt + fr, ks * 32 + fq * 8);
+#pragma unroll
+            for (int kt = 0; kt < 2; kt++) {
+              s[qt][kt] = mma(aq, kreg[kt][ks], s[qt][kt]);
+              dp[qt][kt] = mma(ag, vreg[kt][ks], dp[qt][kt]);
+            }
+          }
+        // P; a pair with no query or no key has P = 0, whatever lse holds there
+#pragma unroll
+        for (int qt = 0; qt < 2; qt++)
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const int q = 32 * j + 16 * qt + 4 * fq + r;  // query within the block
+            const float lq = __shfl(lqs, q & 63, 64);
+#pragma unroll
+            for (int kt = 0; kt < 2; kt++)
+              s[qt][kt][r] = (q < qlive && keyok[kt]) ? __builtin_amdgcn_exp2f(fmaf(s[qt][kt][r], kLog2e, -lq)) : 0.f;
+          }
+        if (diag && j == wave) {  // the one step of this wave the diagonal crosses: key > query has P = 0
+#pragma unroll
+          for (int qt = 0; qt < 2; qt++)
+#pragma unroll
+            for (int kt = 0; kt < 2; kt++)
+#pragma unroll
+              for (int r = 0; r < 4; r++)
+                s[qt][kt][r] = above_diag(16 * qt + 4 * fq + r, 16 * kt + fr, 0.f, s[qt][kt][r]);
+        }
+        floatx4 pd[2][2], ds[2][2];
+#pragma unroll
+        for (int qt = 0; qt < 2; qt++) {
+          const int qb4 = 32 * j + 16 * qt + 4 * fq;
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const float D = __shfl(dds, (qb4 + r) & 63, 64);
+            const uint32_t hh = thresh ? attn_pair_hash(seed, hrow + (uint64_t)(qb4 + r), max_seqlen,
+                                                        blk * BLK + kw + fr)
+                                       : 0u;
+#pragma unroll
+            for (int kt = 0; kt < 2; kt++) {
+              const float p = s[qt][kt][r];
+              float g = dp[qt][kt][r], pv = p;
+              if (thresh) {
+                const bool keep = kt ? keep_hi(hh, thresh) : keep_lo(hh, thresh);
+                pv = keep ? p * dscale : 0.f;
+                g = keep ? g * dscale : 0.f;
+              }
+              pd[qt][kt][r] = pv;
+              ds[qt][kt][r] = p * (g - D);
+            }
+          }
+        }
+        const int ra = 32 * j + 4 * fq, rb = ra + 16;
+        short8 gtr[4], qtr[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; dt++) {
+          gtr[dt] = rd_tr2<64>(Gi, ra, rb, dt * 16, lane);
+          qtr[dt] = rd_tr2<64>(Qi, ra, rb, dt * 16, lane);
+        }
+#pragma unroll
+        for (int kt = 0; kt < 2; kt++) {
+          const short8 bp = pack_pair(pd[0][kt], pd[1][kt]);
+          const short8 bs = pack_pair(ds[0][kt], ds[1][kt]);
+#pragma unroll
+          for (int dt = 0; dt < 4; dt++) {
+            dvT[dt][kt] = mma(gtr[dt], bp, dvT[dt][kt]);
+            dkT[dt][kt] = mma(qtr[dt], bs, dkT[dt][kt]);
+          }
+        }
+      }
+    }
+    __syncthreads();  // the images become the output stage
+    if (!wlive) continue;
+    char* st = sm + wave * 8192;
+    stage_tile(st, dkT, 1.f, fr, fq);
+    stage_tile(st + 4096, dvT, 1.f, fr, fq);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    store_tile_rows(st, dqkv, k0 + kw, W3, H + h * AD, klive - kw, dbqkv, lane);
+    store_tile_rows(st + 4096, dqkv, k0 + kw, W3, 2 * H + h * AD, klive - kw, dbqkv, lane);
+  }
+}
+
+// query-owner dQ = dS·K: query block blk of a pair streams the key blocks 0..blk (K, V images)
+__global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_causal_bwd_q_kernel(
+    const bf16_t* __restrict__ qkv, const float* __restrict__ bqkv, const int* __restrict__ cu,
+    const float* __restrict__ lse, const float* __restrict__ Dq, const bf16_t* __restrict__ dout,
+    bf16_t* __restrict__ dqkv, float* __restrict__ dbqkv, int B, int T, int heads, int max_seqlen, float qscale,
+    uint32_t thresh, float dscale, uint64_t seed) {
+  __shared__ __attribute__((aligned(16))) char sm[2 * 16384];  // K, V images (32 KiB), both passes
+  char* Ki = sm;
+  char* Vi = sm + 16384;
+  const int tid0 = threadIdx.x;
+  CausalPair w;
+  if (!causal_pair(cu, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
+  const int h = w.h, H = heads * AD;
+  const long W3 = 3L * H;
+  if (w.p == 0 && w.b == B - 1) zero_rows(dqkv, W3, h * AD, (long)w.s0 + w.len, T, tid0);
+  const int npass = w.nbs - 1 - w.p != w.p ? 2 : 1;
+#pragma unroll 1
+  for (int pass = 0; pass < npass; pass++) {
+    // the lane's indices are formed again in each pass: held across both, the addresses derived
+    // from them would not fit the register budget
+    int tid = tid0;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
+    const int qb = wave * 32;
+    const int blk = pass ? w.nbs - 1 - w.p : w.p;
+    const long q0 = (long)w.s0 + (long)blk * BLK;
+    const int qlive = min(BLK, w.len - blk * BLK);
+    const bool wlive = qb < qlive;
+    short8 qreg[2][2] = {}, greg[2][2] = {};
+    float lq[2] = {0.f, 0.f}, Dv[2] = {0.f, 0.f};
+    bool qok[2] = {false, false};
+    if (wlive) {
+#pragma unroll
+      for (int qt = 0; qt < 2; qt++) {
+        const int row = qb + 16 * qt + fr;
+        qok[qt] = row < qlive;
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+          const int c = h * AD + ks * 32 + fq * 8;
+          qreg[qt][ks] = row_operand<true>(qkv + (q0 + row) * W3 + c, qok[qt], bqkv + c, qscale);
+          greg[qt][ks] = row_operand<false>(dout + (q0 + row) * H + c, qok[qt], nullptr, 1.f);
+        }
+        if (qok[qt]) {
+          lq[qt] = lse[(long)h * T + q0 + row] * kLog2e;
+          Dv[qt] = Dq[(long)h * T + q0 + row];
+        }
+      }
+    }
+    floatx4 dqT[4][2];
+#pragma unroll
+    for (int dt = 0; dt < 4; dt++) dqT[dt][0] = dqT[dt][1] = floatx4{0.f, 0.f, 0.f, 0.f};
+    const uint64_t hrow = (uint64_t)h * T + (uint64_t)(q0 + qb);
+    for (int j = 0; j <= blk; j++) {  // the loop bound is the mask below the diagonal
+      const int klive = min(BLK, w.len - j * BLK);  // BLK unless j == blk
+      if (j > 0 || pass > 0) __syncthreads();  // every wave is done with the images (or the output stage)
+      {
+        const int col[2] = {H + h * AD, 2 * H + h * AD};
+        const bool tf[2] = {true, true};
+        const float sc[2] = {1.f, 1.f};
+        char* const img[2] = {Ki, Vi};
+        const bf16_t* const src[2] = {qkv, qkv};
+        const long ld[2] = {W3, W3};
+        tail_images<2>(src, ld, (long)w.s0 + (long)j * BLK, col, bqkv, tf, sc, klive, img, tid);
+      }
+      __syncthreads();
+      if (!wlive) continue;
+      // kend as in attn_causal_fwd_kernel: the keys of this block the wave's queries can see
+      const bool diag = j == blk;
+      const int kend = diag ? min(klive, qb + 32) : BLK;
+      // one 32-key slice at a time, as attn_varlen_bwd_q_kernel.  s / dp[u][qt][r]:
+      // (q = qb + 16qt + fr, key = 32c + 16u + 4fq + r), dP(q, key) = dO[q]·V[key]
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        if (c * 32 >= kend) break;
+        floatx4 s[2][2], dp[2][2];
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+          s[u][0] = s[u][1] = dp[u][0] = dp[u][1] = floatx4{0.f, 0.f, 0.f, 0.f};
+          if (c * 32 + u * 16 < kend) {
+#pragma unroll
+            for (int ks = 0; ks < 2; ks++) {
+              const short8 ak = rd_row<64>(Ki, c * 32 + u * 16 + fr, ks * 32 + fq * 8);
+              const short8 av = rd_row<64>(Vi, c * 32 + u * 16 + fr, ks * 32 + fq * 8);
+#pragma unroll
+              for (int qt = 0; qt < 2; qt++) {
+                s[u][qt] = mma(ak, qreg[qt][ks], s[u][qt]);
+                dp[u][qt] = mma(av, greg[qt][ks], dp[u][qt]);
+              }
+            }
+          }
+        }
+        // P; no query: P = 0, whatever lse holds
+#pragma unroll
+        for (int u = 0; u < 2; u++)
+#pragma unroll
+          for (int qt = 0; qt < 2; qt++)
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+              s[u][qt][r] = qok[qt] ? __builtin_amdgcn_exp2f(fmaf(s[u][qt][r], kLog2e, -lq[qt])) : 0.f;
+        if (diag && c * 32 + 31 > qb) {
+          // the slice the diagonal crosses: key > query has P = 0 (a live query's keys at or past
+          // klive are past the query too, so this is the tail rule as well)
+#pragma unroll
+          for (int u = 0; u < 2; u++)
+#pragma unroll
+            for (int qt = 0; qt < 2; qt++)
+#pragma unroll
+              for (int r = 0; r < 4; r++)
+                s[u][qt][r] = above_diag(qb + 16 * qt + fr, c * 32 + 16 * u + 4 * fq + r, 0.f, s[u][qt][r]);
+        }
+#pragma unroll
+        for (int qt = 0; qt < 2; qt++) {
+          const uint64_t row = hrow + (uint64_t)(qt * 16 + fr);
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const uint32_t hh = thresh ? attn_pair_hash(seed, row, max_seqlen, j * BLK + c * 32 + 4 * fq + r) : 0u;
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+              float g = dp[u][qt][r];
+              if (thresh) g = (u ? keep_hi(hh, thresh) : keep_lo(hh, thresh)) ? g * dscale : 0.f;
+              s[u][qt][r] *= g - Dv[qt];  // dS
+            }
+          }
+        }
+        const int ra = 32 * c + 4 * fq, rb = ra + 16;
+        short8 ktr[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; dt++) ktr[dt] = rd_tr2<64>(Ki, ra, rb, dt * 16, lane);
+#pragma unroll
+        for (int qt = 0; qt < 2; qt++) {
+          const short8 bs = pack_pair(s[0][qt], s[1][qt]);
+#pragma unroll
+          for (int dt = 0; dt < 4; dt++) dqT[dt][qt] = mma(ktr[dt], bs, dqT[dt][qt]);
+        }
+      }
+    }
+    __syncthreads();  // the K image becomes the output stage
+    if (!wlive) continue;
+    char* st = sm + wave * 4096;
+    stage_tile(st, dqT, qscale, fr, fq);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    store_tile_rows(st, dqkv, q0 + qb, W3, h * AD, qlive - qb, dbqkv, lane);
+  }
+}
+
 // t16 = round(p·2^16) (0: no dropout) and the keep scale 2^16 / (2^16 − t16)
 uint32_t attn_drop_t16(float p) {
   if (!(p > 0.f)) return 0u;
@@ -1833,6 +2357,41 @@ KFA_API int kfa_attn_varlen_bwd(const void* qkv, const float* bqkv, const int* c
   hipLaunchKernelGGL(attn_varlen_bwd_kv_kernel, grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu, lse, work,
                      (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th, ds, (uint64_t)seed);
   hipLaunchKernelGGL(attn_varlen_bwd_q_kernel, grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu, lse, work,
+                     (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th, ds, (uint64_t)seed);
+  return kfa_status();
+}
+
+// Causal attention over a packed batch (see attn_causal_fwd_kernel): the parameters and checks of
+// kfa_attn_varlen_fwd / bwd; one workgroup per (sequence, head, pair of 128-row blocks)
+static unsigned attn_causal_grid(int B, int max_seqlen, int heads) {
+  return (unsigned)((long)B * heads * (((max_seqlen + BLK - 1) / BLK + 1) / 2));
+}
+
+KFA_API int kfa_attn_causal_fwd(const void* qkv, const float* bqkv, const int* cu, void* out, float* lse, int B, int T,
+                                int max_seqlen, int heads, int d, float qscale, float p, unsigned long long seed,
+                                hipStream_t st) {
+  if (!qkv || !bqkv || !cu || !out || !lse || !attn_varlen_args_ok(B, T, max_seqlen, heads, d)) return -1;
+  const uint32_t th = attn_drop_t16(p);
+  hipLaunchKernelGGL(attn_causal_fwd_kernel, dim3(attn_causal_grid(B, max_seqlen, heads)), dim3(256), 0, st,
+                     (const bf16_t*)qkv, bqkv, cu, (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th,
+                     attn_drop_scale(th), (uint64_t)seed);
+  return kfa_status();
+}
+
+KFA_API int kfa_attn_causal_bwd(const void* qkv, const float* bqkv, const int* cu, const void* out, const float* lse,
+                                const void* dout, void* dqkv, float* dbqkv, int B, int T, int max_seqlen, int heads,
+                                int d, float qscale, float p, unsigned long long seed, float* work, hipStream_t st) {
+  if (!qkv || !bqkv || !cu || !out || !lse || !dout || !dqkv || !attn_varlen_args_ok(B, T, max_seqlen, heads, d))
+    return -1;
+  if (!work) return -3;
+  const uint32_t th = attn_drop_t16(p);
+  const float ds = attn_drop_scale(th);
+  hipLaunchKernelGGL(attn_varlen_rowdot_kernel, dim3((unsigned)(((long)T * heads + 255) / 256)), dim3(256), 0, st,
+                     (const bf16_t*)dout, (const bf16_t*)out, cu, work, B, T, heads);
+  const dim3 grid(attn_causal_grid(B, max_seqlen, heads));
+  hipLaunchKernelGGL(attn_causal_bwd_kv_kernel, grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu, lse, work,
+                     (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th, ds, (uint64_t)seed);
+  hipLaunchKernelGGL(attn_causal_bwd_q_kernel, grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu, lse, work,
                      (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th, ds, (uint64_t)seed);
   return kfa_status();
 }

@@ -1,0 +1,174 @@
+"""GPT decoder-only language model (the GPT-1 arrangement: post-LN blocks).
+
+A post-LN decoder block is the project's encoder layer with causal attention, so the
+model reuses :class:`~kubeflow_controller_amd.models.bert.BertLayer` parameters and
+every fused kernel of :class:`~kubeflow_controller_amd.ops.transformer.EncoderLayerFn`;
+attention runs on the causal packed kernels (``csrc/kernels/attention.hip``:
+attn_causal_*), which compute only the visible half of the score matrix.
+
+Batches are always packed (:class:`~kubeflow_controller_amd.ops.transformer.PackedSeqs`):
+documents of any length back to back in a fixed budget of token rows; a padded batch
+of S tokens is the table ``[0, S, 2S, …]``.  The loss is next-token cross-entropy over
+the WHOLE row budget: the label of a row is the next token of its sequence, -1 (ignored
+by the loss kernel) for a sequence's last token and for the unowned rows.  The decoder
+GEMM's M is therefore the row budget, whatever the batch holds, and its route never
+changes; the tied decoder keeps a bias (zero-initialised) as BERT's does, because the
+loss kernel produces its gradient anyway.
+
+Vocabulary is padded to a multiple of 64 (50257 → 50304); padded ids never occur as
+inputs or labels.
+
+CPU path: the same parameters through plain PyTorch fp32 ops (no dropout).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from ..ops import transformer as T
+from .bert import BertLayer
+
+
+@dataclass
+class GptConfig:
+    vocab_size: int = 50257
+    hidden: int = 768
+    layers: int = 12
+    heads: int = 12
+    intermediate: int = 3072
+    max_position: int = 1024
+    hidden_dropout: float = 0.1
+    attn_dropout: float = 0.1
+    ln_eps: float = 1e-5
+    init_range: float = 0.02
+
+    @classmethod
+    def small(cls) -> "GptConfig":
+        return cls()
+
+    @classmethod
+    def tiny(cls) -> "GptConfig":
+        return cls(vocab_size=1000, hidden=128, layers=2, heads=2, intermediate=512, max_position=256)
+
+    @property
+    def padded_vocab(self) -> int:
+        return (self.vocab_size + 63) // 64 * 64
+
+
+def next_token_labels(input_ids, seqs: T.PackedSeqs):
+    """int64 [rows] on the host: row t's label is the token of row t + 1 of the same
+    sequence; -1 for every sequence's last token (rows ``cu[1:] - 1``) and the unowned rows."""
+    ids = input_ids.reshape(-1).cpu()
+    labels = torch.full_like(ids, -1)
+    n = seqs.tokens
+    labels[:n - 1] = ids[1:n]
+    labels[seqs.cu_host[1:].long() - 1] = -1
+    return labels
+
+
+class GptLM(nn.Module):
+    def __init__(self, cfg: GptConfig, seed: int = 0):
+        super().__init__()
+        self.cfg = cfg
+        H, V = cfg.hidden, cfg.padded_vocab
+        self.word_emb = nn.Parameter(torch.empty(V, H))
+        self.pos_emb = nn.Parameter(torch.empty(cfg.max_position, H))
+        for w in (self.word_emb, self.pos_emb):
+            nn.init.normal_(w, 0.0, cfg.init_range)
+        self.layers = nn.ModuleList(BertLayer(cfg) for _ in range(cfg.layers))
+        self.dec_b = nn.Parameter(torch.zeros(V))
+        # the word embedding is written by two direct-gradient kernels per step (lookup
+        # and tied decoder), as BertForPreTraining's
+        self.word_emb._kfa_uses = 2
+        self._kfa_param_uses = {"word_emb": 2}
+        self.seed = seed
+        self._step = 0
+
+    @property
+    def graph_capturable(self) -> bool:
+        """The packed batch carries a host sequence table that is checked before every launch."""
+        return False
+
+    def forward(self, input_ids, position_ids, seqs, labels):
+        """Mean next-token cross-entropy over the rows that have a target.  ``input_ids``,
+        ``position_ids``, ``labels`` (:func:`next_token_labels`): flat [rows]; ``seqs``: the table."""
+        cfg = self.cfg
+        if seqs.max_seqlen > cfg.max_position:
+            raise ValueError(f"GptLM: max_seqlen {seqs.max_seqlen} exceeds max_position {cfg.max_position}")
+        rows = input_ids.numel()
+        seqs.validate(rows)
+        if not input_ids.is_cuda:
+            return self.forward_reference(input_ids, position_ids, seqs, labels)
+        ph = cfg.hidden_dropout if self.training else 0.0
+        pa = cfg.attn_dropout if self.training else 0.0
+        step_seed = T.mix_seed(self.seed, self._step)
+        if self.training:
+            self._step += 1
+        h = T.embedding_sum([self.word_emb, self.pos_emb], [input_ids.reshape(-1), position_ids.reshape(-1)])
+        if ph > 0:
+            h = T.dense_dropout(h, ph, T.mix_seed(step_seed, 999))
+        join_in = None
+        for i, layer in enumerate(self.layers):
+            join_out = T.ResidualJoin() if (self.training and i + 1 < len(self.layers)) else None
+            lcfg = (seqs.B, seqs.max_seqlen, cfg.heads, ph, pa, T.s64(T.mix_seed(step_seed, i)), cfg.ln_eps, join_in,
+                    join_out, seqs, True)
+            h = T.EncoderLayerFn.apply(h, None, lcfg, *layer.params())
+            join_in = join_out
+        # decoder_xent means over all rows (ignored rows add 0): rescale to the rows with a
+        # target, a host integer (every sequence has len - 1 of them)
+        targets = seqs.tokens - seqs.B
+        if targets <= 0:
+            raise ValueError("GptLM: no row has a target (every sequence is a single token)")
+        return T.decoder_xent(h, self.word_emb, self.dec_b, labels.reshape(-1)) * (rows / targets)
+
+    def forward_reference(self, input_ids, position_ids, seqs, labels):
+        """Plain PyTorch fp32, no dropout (CPU replicas + numerics reference)."""
+        cfg = self.cfg
+        f = lambda t: t.float()  # noqa: E731
+        h = f(self.word_emb)[input_ids.reshape(-1)] + f(self.pos_emb)[position_ids.reshape(-1)]
+        lcfg = (seqs.B, seqs.max_seqlen, cfg.heads, 0.0, 0.0, 0, cfg.ln_eps, None, None, seqs, True)
+        for layer in self.layers:
+            h = T.encoder_layer_reference(h, None, lcfg, *layer.params())
+        logits = h @ f(self.word_emb).t() + f(self.dec_b)
+        return F.cross_entropy(logits, labels.reshape(-1), ignore_index=-1)
+
+
+def gpt_loss(model, *batch):
+    return model(*batch)
+
+
+def synthetic_lm_batch(cfg: GptConfig, rows: int, seq_len: int, min_len: int, generator=None, device="cpu"):
+    """Random documents in the style of ``synthetic_packed_mlm_batch``: lengths uniform in
+    [min_len, seq_len], added while they fit in ``rows`` token rows (the remainder stays
+    unowned).  Returns the positional args of :meth:`GptLM.forward`."""
+    g = generator
+    if not 2 <= min_len <= seq_len <= rows:
+        raise ValueError(f"synthetic_lm_batch: need 2 <= min_len <= seq_len <= rows, got {min_len}, {seq_len}, {rows}")
+    lens = []
+    while True:
+        n = int(torch.randint(min_len, seq_len + 1, (1,), generator=g))
+        if sum(lens) + n > rows:
+            break
+        lens.append(n)
+    cu = torch.tensor([0] + lens).cumsum(0)
+    ids = torch.zeros(rows, dtype=torch.int64)
+    ids[:cu[-1]] = torch.randint(0, cfg.vocab_size, (int(cu[-1]),), generator=g)
+    pos_ids = torch.zeros(rows, dtype=torch.int64)
+    for i, n in enumerate(lens):
+        pos_ids[int(cu[i]):int(cu[i]) + n] = torch.arange(n)
+    seqs = T.PackedSeqs(cu, rows, seq_len, device)
+    to = lambda t: t.to(device)  # noqa: E731
+    return to(ids), to(pos_ids), seqs, to(next_token_labels(ids, seqs))
+
+
+def flops_per_step(cfg: GptConfig, lens) -> float:
+    """Model FLOPs (fwd+bwd = 3x fwd) of one step on sequences of ``lens`` tokens; attention
+    counts the visible half of each score matrix."""
+    Tk = float(sum(lens))
+    H, I, L = cfg.hidden, cfg.intermediate, cfg.layers
+    attn = sum(2 * 2 * (n * (n + 1) / 2) * H for n in lens)
+    per_layer = 2 * Tk * (3 * H * H + H * H + 2 * H * I) + attn
+    return 3.0 * (L * per_layer + 2 * Tk * H * cfg.padded_vocab)

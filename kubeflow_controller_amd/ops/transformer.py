@@ -62,6 +62,8 @@ _lib.register("kfa_attn_dbias_part_floats", [I, I], L)
 _lib.register("kfa_attn_mask_words", [I, I, I], _lib.L)
 _lib.register("kfa_attn_varlen_fwd", [P, P, P, P, P, I, I, I, I, I, Fl, Fl, U64, P])
 _lib.register("kfa_attn_varlen_bwd", [P, P, P, P, P, P, P, P, I, I, I, I, I, Fl, Fl, U64, P, P])
+_lib.register("kfa_attn_causal_fwd", [P, P, P, P, P, I, I, I, I, I, Fl, Fl, U64, P])
+_lib.register("kfa_attn_causal_bwd", [P, P, P, P, P, P, P, P, I, I, I, I, I, Fl, Fl, U64, P, P])
 
 # env KFA_FUSED_ATTN=0 falls back to the split kernels + batched library GEMMs
 FUSED_ATTN = os.environ.get("KFA_FUSED_ATTN", "1") != "0"
@@ -609,25 +611,27 @@ def _varlen_check(name, qkv, bqkv, seqs, heads):
     return bqkv
 
 
-def attn_varlen_fwd(qkv, bqkv, seqs: PackedSeqs, heads, p=0.0, seed=0):
+def attn_varlen_fwd(qkv, bqkv, seqs: PackedSeqs, heads, p=0.0, seed=0, causal=False):
     """(ctx [T, H], lse [heads, T]) of per-sequence softmax((q+b)(k+b)ᵀ/√d)·(v+b) over the
     packed batch ``seqs`` (``csrc/kernels/attention.hip``: attn_varlen_fwd_kernel); the
     unowned rows of ctx are zero.  Dropout: hash row ``h·T + token row``, key index
-    within the sequence (attn_pair_hash with S = max_seqlen)."""
+    within the sequence (attn_pair_hash with S = max_seqlen).  ``causal``: query i sees
+    keys 0..i of its sequence (attn_causal_fwd_kernel: the masked half is not computed)."""
     bqkv = _varlen_check("attn_varlen_fwd", qkv, bqkv, seqs, heads)
     T_, W3 = qkv.shape
     H = W3 // 3
     out = torch.empty(T_, H, dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty(heads, T_, dtype=torch.float32, device=qkv.device)
-    _lib.call("kfa_attn_varlen_fwd", _lib.ptr(qkv), _lib.ptr(bqkv), _lib.ptr(seqs.cu_dev), _lib.ptr(out),
-              _lib.ptr(lse), seqs.B, T_, seqs.max_seqlen, heads, 64, 1.0 / math.sqrt(64), float(p), hash_key(seed),
+    _lib.call("kfa_attn_causal_fwd" if causal else "kfa_attn_varlen_fwd", _lib.ptr(qkv), _lib.ptr(bqkv),
+              _lib.ptr(seqs.cu_dev), _lib.ptr(out), _lib.ptr(lse), seqs.B, T_, seqs.max_seqlen, heads, 64, 1.0 / math.sqrt(64), float(p), hash_key(seed),
               _lib.stream())
     return out, lse
 
 
-def attn_varlen_bwd(qkv, bqkv, seqs: PackedSeqs, out, lse, dout, dbqkv, heads, p=0.0, seed=0):
+def attn_varlen_bwd(qkv, bqkv, seqs: PackedSeqs, out, lse, dout, dbqkv, heads, p=0.0, seed=0, causal=False):
     """dqkv [T, 3H] of :func:`attn_varlen_fwd` (``out``, ``lse``: its outputs; unowned rows
-    zero); the bias gradient is added into ``dbqkv`` (fp32 [3H], nullable)."""
+    zero); the bias gradient is added into ``dbqkv`` (fp32 [3H], nullable).  ``causal`` as
+    the forward's (attn_causal_bwd_kv_kernel / attn_causal_bwd_q_kernel)."""
     bqkv = _varlen_check("attn_varlen_bwd", qkv, bqkv, seqs, heads)
     T_, W3 = qkv.shape
     H = W3 // 3
@@ -644,16 +648,17 @@ def attn_varlen_bwd(qkv, bqkv, seqs: PackedSeqs, out, lse, dout, dbqkv, heads, p
         raise ValueError("attn_varlen_bwd: dbqkv must be a contiguous fp32 [3H] vector")
     dqkv = torch.empty_like(qkv)
     work = _lib.workspace(heads * T_ * 4, qkv.device, "attn_rowdot")  # D = rowsum(dO∘O) [heads, T]
-    _lib.call("kfa_attn_varlen_bwd", _lib.ptr(qkv), _lib.ptr(bqkv), _lib.ptr(seqs.cu_dev), _lib.ptr(out),
-              _lib.ptr(lse), _lib.ptr(dout), _lib.ptr(dqkv), _lib.ptr(dbqkv), seqs.B, T_, seqs.max_seqlen, heads, 64,
+    _lib.call("kfa_attn_causal_bwd" if causal else "kfa_attn_varlen_bwd", _lib.ptr(qkv), _lib.ptr(bqkv),
+              _lib.ptr(seqs.cu_dev), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(dout), _lib.ptr(dqkv), _lib.ptr(dbqkv), seqs.B, T_, seqs.max_seqlen, heads, 64,
               1.0 / math.sqrt(64), float(p), hash_key(seed), _lib.ptr(work), _lib.stream())
     return dqkv
 
 
-def attention_varlen_reference(qkv, bqkv, seqs: PackedSeqs, heads, keep=None, keep_scale=1.0):
+def attention_varlen_reference(qkv, bqkv, seqs: PackedSeqs, heads, keep=None, keep_scale=1.0, causal=False):
     """Plain fp32 PyTorch: ctx [T, H] of the packed batch, one sequence at a time; the
     unowned rows are zero.  ``keep`` (optional): per sequence a [heads, len, len] 0/1
-    dropout keep mask, kept probabilities scaled by ``keep_scale``."""
+    dropout keep mask, kept probabilities scaled by ``keep_scale``.  ``causal``: scores
+    above each sequence's diagonal are -inf before the softmax."""
     T_, W3 = qkv.shape
     H = W3 // 3
     d = H // heads
@@ -664,7 +669,10 @@ def attention_varlen_reference(qkv, bqkv, seqs: PackedSeqs, heads, keep=None, ke
     parts = []
     for i in range(len(cu) - 1):
         q, k, v = x[cu[i]:cu[i + 1]].view(-1, 3, heads, d).permute(1, 2, 0, 3)   # [heads, len, d]
-        pr = torch.softmax((q @ k.transpose(-1, -2)) / math.sqrt(d), -1)
+        sc = (q @ k.transpose(-1, -2)) / math.sqrt(d)
+        if causal:
+            sc = sc.masked_fill(~torch.tril(torch.ones_like(sc, dtype=torch.bool)), float("-inf"))
+        pr = torch.softmax(sc, -1)
         if keep is not None:
             pr = pr * keep[i] * keep_scale
         parts.append((pr @ v).permute(1, 0, 2).reshape(-1, H))
@@ -733,10 +741,14 @@ class EncoderLayerFn(torch.autograd.Function):
         # cfg[7:9] (optional): ResidualJoin of this layer's input (deposited into by
         # the backward) and of its output (taken from by the backward); cfg[9] (optional):
         # the PackedSeqs of a packed batch — x is then [rows, H], attention runs per
-        # sequence through the varlen kernels (B and S are not used) and key_bias is None
+        # sequence through the varlen kernels (B and S are not used) and key_bias is None;
+        # cfg[10] (optional): causal attention (a decoder layer), packed batches only
         B, S, heads, ph, pa, seed, eps = cfg[:7]
         ctx.joins = (tuple(cfg[7:9]) + (None, None))[:2]
         seqs = cfg[9] if len(cfg) > 9 else None
+        causal = bool(cfg[10]) if len(cfg) > 10 else False
+        if causal and seqs is None:
+            raise ValueError("EncoderLayerFn: causal attention needs a packed batch (cfg[9]: a PackedSeqs)")
         _gemm.mark_weights_stale()  # the dgrad's cached weight transposes refresh at the next backward
         T, H = x.shape
         d = H // heads
@@ -758,7 +770,7 @@ class EncoderLayerFn(torch.autograd.Function):
         # attention
         qkv = mm(x, wqkv)                                                 # [T, 3H]
         if seqs is not None:
-            ctxr, lse = attn_varlen_fwd(qkv, bqkv, seqs, heads, pa, s_attn)
+            ctxr, lse = attn_varlen_fwd(qkv, bqkv, seqs, heads, pa, s_attn, causal=causal)
             att = (qkv, lse)
         elif fused:
             ctxr, lse, amask = attn_fwd(qkv, bqkv, key_bias, B, S, heads, pa, s_attn, want_mask=True) if ATTN_MASK \
@@ -796,6 +808,7 @@ class EncoderLayerFn(torch.autograd.Function):
         ctx.cfg = (B, S, heads, ph, pa, (s_attn, s_h1, s_h2), qscale, use_g, use_f, fused, z_bias)
         ctx.key_bias = key_bias
         ctx.seqs = seqs
+        ctx.causal = causal
         return h2
 
     @staticmethod
@@ -837,7 +850,7 @@ class EncoderLayerFn(torch.autograd.Function):
         del dao
         if ctx.seqs is not None:
             qkv, lse = att
-            dqkv = attn_varlen_bwd(qkv, bqkv, ctx.seqs, ctxr, lse, dctxr, None, heads, pa, s_attn)
+            dqkv = attn_varlen_bwd(qkv, bqkv, ctx.seqs, ctxr, lse, dctxr, None, heads, pa, s_attn, causal=ctx.causal)
             colsum_(dqkv, G(bqkv))  # as the fused path: one column-sum pass over the still-cached dqkv
             del dctxr
         elif fused:
@@ -886,9 +899,13 @@ class EncoderLayerFn(torch.autograd.Function):
 
 def encoder_layer_reference(x, key_bias, cfg, wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2):
     """Plain PyTorch fp32 reference (no dropout); cfg[9] (optional): the PackedSeqs of a
-    packed batch (x [rows, H], attention per sequence, no key_bias)."""
+    packed batch (x [rows, H], attention per sequence, no key_bias); cfg[10] (optional):
+    causal attention, packed batches only."""
     B, S, heads, _, _, _, eps = cfg[:7]
     seqs = cfg[9] if len(cfg) > 9 else None
+    causal = bool(cfg[10]) if len(cfg) > 10 else False
+    if causal and seqs is None:
+        raise ValueError("encoder_layer_reference: causal attention needs a packed batch (cfg[9])")
     T, H = x.shape
     d = H // heads
     f = lambda t: t.float()  # noqa: E731
@@ -897,7 +914,7 @@ def encoder_layer_reference(x, key_bias, cfg, wqkv, bqkv, wo, bo, g1, be1, w1, b
     if seqs is not None:
         if key_bias is not None:
             raise ValueError("encoder_layer_reference: a packed batch takes no key_bias")
-        a = attention_varlen_reference(qkv, None, seqs, heads)
+        a = attention_varlen_reference(qkv, None, seqs, heads, causal=causal)
     else:
         q, k, v = qkv.view(B, S, 3, heads, d).permute(2, 0, 3, 1, 4)
         sc = (q @ k.transpose(-1, -2)) / math.sqrt(d)

@@ -147,6 +147,10 @@ def build(args, device):
         from ..models.bert import BertConfig, BertForPreTraining, bert_loss
         cfg = BertConfig.base() if name == "bert_base" else BertConfig.tiny()
         return BertForPreTraining(cfg), None, bert_loss
+    if name in ("gpt_small", "gpt_tiny"):
+        from ..models.gpt import GptConfig, GptLM, gpt_loss
+        cfg = GptConfig.small() if name == "gpt_small" else GptConfig.tiny()
+        return GptLM(cfg), None, gpt_loss
     if name in ("wide_deep", "wide_deep_tiny"):
         from ..models.wide_deep import WideDeep, WideDeepConfig, wide_deep_loss
         cfg = WideDeepConfig() if name == "wide_deep" else WideDeepConfig.tiny()
@@ -208,6 +212,10 @@ def synthetic_batch(args, model, device, rank: int):
             return synthetic_packed_mlm_batch(model.cfg, B * args.seq_len, args.seq_len,
                                               min(args.min_seq_len, args.seq_len), g, device)
         return synthetic_mlm_batch(model.cfg, B, args.seq_len, g, device)
+    if args.model.startswith("gpt"):  # always packed: documents of [--min_seq_len, --seq_len] tokens
+        from ..models.gpt import synthetic_lm_batch
+        return synthetic_lm_batch(model.cfg, B * args.seq_len, args.seq_len,
+                                  max(2, min(args.min_seq_len, args.seq_len)), g, device)
     if args.model.startswith("wide_deep"):
         from ..models.wide_deep import prepare_batch
         from ..models.wide_deep import synthetic_batch as wd_batch
@@ -536,7 +544,7 @@ def run_worker(spec: ClusterSpec, args) -> int:
     # step of more than GRAPH_AUTO_MS keeps eager launches (ResNet-50 at batch 256:
     # 21.8 ms eager, replay measured 0.5 % slower; the reference's MNIST: 0.2 ms).
     use_graph = args.graph == "on" or (args.graph == "auto" and world == 1 and device.type == "cuda")
-    if args.pack_sequences and args.model.startswith("bert"):
+    if (args.pack_sequences and args.model.startswith("bert")) or args.model.startswith("gpt"):
         use_graph = False  # the packed batch carries a host sequence table that is checked before every launch
     cap_step = 1 if args.graph == "on" else 2
     if hasattr(data, "eval_batches"):  # image dataset: resident in HBM or staged through pinned buffers
@@ -634,7 +642,8 @@ def build_parser() -> argparse.ArgumentParser:
     add_cluster_flags(ap)
     ap.add_argument("--model", default="mnist_mlp",
                     help="mnist_softmax | mnist_mlp | resnet50 | resnet_tiny | bert_base | bert_tiny | "
-                         "wide_deep | wide_deep_tiny")
+                         "gpt_small | gpt_tiny | wide_deep | wide_deep_tiny (the gpt models always train on "
+                         "packed documents of [--min_seq_len, --seq_len] tokens in batch_size * seq_len rows)")
     ap.add_argument("--train_steps", type=int, default=200)
     ap.add_argument("--batch_size", type=int, default=100)
     ap.add_argument("--learning_rate", type=float, default=0.01)
@@ -654,7 +663,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--pack_sequences", action="store_true",
                     help="BERT: train on variable-length sequences (lengths uniform in [--min_seq_len, --seq_len]) "
                          "packed into batch_size * seq_len token rows instead of a padded [batch_size, seq_len] batch")
-    ap.add_argument("--min_seq_len", type=int, default=16, help="shortest sequence of a --pack_sequences batch")
+    ap.add_argument("--min_seq_len", type=int, default=16, help="shortest sequence of a --pack_sequences (or gpt) batch")
     ap.add_argument("--sync_replicas", action="store_true")
     ap.add_argument("--ps_mode", default="auto", choices=["auto", "async", "collective"],
                     help="async: PS tasks own variables + Adam (reference default); collective: RCCL "

@@ -43,11 +43,48 @@ def alternate(sides, rounds, iters):
     return {k: (min(v), statistics.median(v)) for k, v in t.items()}
 
 
+def causal(rounds):
+    """--causal: one BERT-base-shaped layer (12 heads, dropout 0.1), the causal kernels against the
+    bidirectional varlen kernels on the SAME packed batch: 32 sequences of 1024 tokens, and
+    lengths uniform in [128, 1024]."""
+    d = torch.device("cuda")
+    g = torch.Generator().manual_seed(0)
+    torch.manual_seed(0)
+    h, p, S = 12, 0.1, 1024
+    H = h * 64
+    for name, lens in (("32 x 1024", torch.full((32,), S)), ("32, uniform in [128, 1024]",
+                                                            torch.randint(128, S + 1, (32,), generator=g))):
+        rows = int(lens.sum())
+        seqs = T.PackedSeqs(torch.cat([torch.zeros(1, dtype=torch.long), lens.cumsum(0)]), rows, S, d)
+        qkv = torch.randn(rows, 3 * H, device=d).to(torch.bfloat16)
+        dout = torch.randn(rows, H, device=d).to(torch.bfloat16)
+        bqkv = torch.randn(3 * H, device=d) * 0.1
+
+        def both(c):
+            out, lse = T.attn_varlen_fwd(qkv, bqkv, seqs, h, p, 7, causal=c)
+            T.attn_varlen_bwd(qkv, bqkv, seqs, out, lse, dout, None, h, p, 7, causal=c)
+
+        sides = {"bidirectional fwd": lambda: T.attn_varlen_fwd(qkv, bqkv, seqs, h, p, 7),
+                 "causal fwd": lambda: T.attn_varlen_fwd(qkv, bqkv, seqs, h, p, 7, causal=True),
+                 "bidirectional fwd+bwd": lambda: both(False), "causal fwd+bwd": lambda: both(True)}
+        r = alternate(sides, rounds, 20)
+        nb = (lens + 127) // 128
+        print(f"attention, {name}: {rows} rows; 128-row blocks streamed causal / bidirectional = "
+              f"{float((nb * (nb + 1) / 2).sum() / (nb * nb).sum()):.4f}")
+        for k, (lo, med) in r.items():
+            print(f"  {k:22s} min {lo * 1e3:7.1f} us  median {med * 1e3:7.1f} us", flush=True)
+        for k in ("fwd", "fwd+bwd"):
+            print(f"  causal / bidirectional {k}: {r['causal ' + k][0] / r['bidirectional ' + k][0]:.3f} (min over rounds)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--causal", action="store_true", help="causal vs bidirectional varlen kernels at 1024 tokens")
     args = ap.parse_args()
+    if args.causal:
+        return causal(args.rounds)
     d = torch.device("cuda")
     g = torch.Generator().manual_seed(0)
     torch.manual_seed(0)

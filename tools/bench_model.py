@@ -25,12 +25,14 @@ from kubeflow_controller_amd.trainer.engine import Engine, init_distributed, tim
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__)
-    ap.add_argument("--model", default="bert_base", choices=["bert_base", "bert_large", "bert_tiny", "wide_deep",
-                                                             "wide_deep_tiny"])
+    ap.add_argument("--model", default="bert_base", choices=["bert_base", "bert_large", "bert_tiny", "gpt_small",
+                                                             "gpt_tiny", "wide_deep", "wide_deep_tiny"])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--batch", type=int, default=64, help="per-GPU batch")
-    ap.add_argument("--seq", type=int, default=128)
+    ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 64; gpt: 8)")
+    ap.add_argument("--seq", type=int, default=None, help="sequence length (default 128; gpt: 1024, the longest "
+                    "document of a packed batch of batch * seq token rows)")
+    ap.add_argument("--min-seq", type=int, default=128, help="gpt: the shortest document")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--ps", type=int, default=0, help="parameter-server shard owners (0 = all-reduce)")
     ap.add_argument("--bucket-mb", type=float, default=32.0)
@@ -38,6 +40,10 @@ def main(argv=None) -> int:
     ap.add_argument("--max-grad-norm", type=float, default=None,
                     help="clip the gradient to this global L2 norm (all-reduce layout only)")
     args = ap.parse_args(argv)
+    gpt = args.model.startswith("gpt")
+    # gpt_small: 8 x 1024 = 8192 rows keeps the bf16 logits and their gradient (rows x 50304 each) at 0.8 GB apiece
+    args.batch = args.batch if args.batch is not None else (8 if gpt else 64)
+    args.seq = args.seq if args.seq is not None else (1024 if args.model == "gpt_small" else 128)
     info = init_distributed()
     if info.device.type != "cuda":
         raise SystemExit("bench_model.py needs an MI355X")
@@ -51,6 +57,16 @@ def main(argv=None) -> int:
         batch = synthetic_mlm_batch(cfg, args.batch, args.seq, g, info.device)
         loss_fn, unit, flops = bert_loss, "sequences/sec", flops_per_step(cfg, args.batch, args.seq)
         metric = f"{args.model} pre-training sequences/sec (seq {args.seq}, whole node)"
+    elif gpt:
+        from kubeflow_controller_amd.models.gpt import GptConfig, GptLM, flops_per_step, gpt_loss, synthetic_lm_batch
+        cfg = GptConfig.small() if args.model == "gpt_small" else GptConfig.tiny()
+        model = GptLM(cfg)
+        batch = synthetic_lm_batch(cfg, args.batch * args.seq, args.seq, min(args.min_seq, args.seq), g, info.device)
+        cu = batch[2].cu_host
+        loss_fn, unit, flops = gpt_loss, "sequences/sec", flops_per_step(cfg, (cu[1:] - cu[:-1]).tolist())
+        metric = (f"{args.model} LM training sequences/sec ({batch[2].B} packed documents of {args.min_seq}..{args.seq} "
+                  f"tokens, {batch[2].tokens} live of {args.batch * args.seq} rows, whole node)")
+        args.batch = batch[2].B  # sequences per step
     else:
         from kubeflow_controller_amd.models.wide_deep import (WideDeep, WideDeepConfig, prepare_batch, synthetic_batch,
                                                               wide_deep_loss)
@@ -70,7 +86,7 @@ def main(argv=None) -> int:
                "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
                "vs_baseline": None, "dtype": "bf16", "data": "synthetic (random ids / features, random-init weights)",
                "config": {"model": args.model, "global_batch": args.batch * info.world,
-                          "seq_len": args.seq if args.model.startswith("bert") else None,
+                          "seq_len": args.seq if args.model.startswith(("bert", "gpt")) else None,
                           "parallelism": (f"{info.world}w+{args.ps}ps" if args.ps else f"dp{info.world}"),
                           "optimizer": args.optimizer, "max_grad_norm": args.max_grad_norm,
                           "routes": _routes.summary(), "loss": r["loss"]}}
