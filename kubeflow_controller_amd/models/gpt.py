@@ -50,6 +50,13 @@ class GptConfig:
         return cls()
 
     @classmethod
+    def xl(cls) -> "GptConfig":
+        """GPT-3 XL shape: 24 layers of 2048 with 16 heads of 128 (the d = 128 causal kernels);
+        1.32 B parameters (24 x 50.4 M of layers + 103 M of tied token and 4 M of position
+        embeddings)."""
+        return cls(hidden=2048, layers=24, heads=16, intermediate=8192, max_position=2048)
+
+    @classmethod
     def tiny(cls) -> "GptConfig":
         return cls(vocab_size=1000, hidden=128, layers=2, heads=2, intermediate=512, max_position=256)
 

@@ -598,8 +598,8 @@ def _varlen_check(name, qkv, bqkv, seqs, heads):
     if qkv.dim() != 2 or qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
         raise ValueError(f"{name}: qkv must be a contiguous bf16 [T, 3H] tensor")
     T_, W3 = qkv.shape
-    if heads <= 0 or W3 % (3 * heads) or W3 // (3 * heads) != 64:
-        raise ValueError(f"{name}: head dim must be 64 (qkv {tuple(qkv.shape)}, heads={heads})")
+    if heads <= 0 or W3 % (3 * heads) or W3 // (3 * heads) not in (64, 128):
+        raise ValueError(f"{name}: head dim must be 64 or 128 (qkv {tuple(qkv.shape)}, heads={heads})")
     seqs.validate(T_)
     if not qkv.is_cuda or seqs.cu_dev.device != qkv.device:
         raise ValueError(f"{name}: qkv and the sequence table must be on the same GPU "
@@ -613,17 +613,18 @@ def _varlen_check(name, qkv, bqkv, seqs, heads):
 
 def attn_varlen_fwd(qkv, bqkv, seqs: PackedSeqs, heads, p=0.0, seed=0, causal=False):
     """(ctx [T, H], lse [heads, T]) of per-sequence softmax((q+b)(k+b)ᵀ/√d)·(v+b) over the
-    packed batch ``seqs`` (``csrc/kernels/attention.hip``: attn_varlen_fwd_kernel); the
-    unowned rows of ctx are zero.  Dropout: hash row ``h·T + token row``, key index
+    packed batch ``seqs`` (``csrc/kernels/attention.hip``: attn_varlen_fwd_kernel; head dim
+    128: ``attention_d128.hip``, same contracts); the unowned rows of ctx are zero.  Dropout: hash row ``h·T + token row``, key index
     within the sequence (attn_pair_hash with S = max_seqlen).  ``causal``: query i sees
     keys 0..i of its sequence (attn_causal_fwd_kernel: the masked half is not computed)."""
     bqkv = _varlen_check("attn_varlen_fwd", qkv, bqkv, seqs, heads)
     T_, W3 = qkv.shape
     H = W3 // 3
+    d = H // heads
     out = torch.empty(T_, H, dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty(heads, T_, dtype=torch.float32, device=qkv.device)
     _lib.call("kfa_attn_causal_fwd" if causal else "kfa_attn_varlen_fwd", _lib.ptr(qkv), _lib.ptr(bqkv),
-              _lib.ptr(seqs.cu_dev), _lib.ptr(out), _lib.ptr(lse), seqs.B, T_, seqs.max_seqlen, heads, 64, 1.0 / math.sqrt(64), float(p), hash_key(seed),
+              _lib.ptr(seqs.cu_dev), _lib.ptr(out), _lib.ptr(lse), seqs.B, T_, seqs.max_seqlen, heads, d, 1.0 / math.sqrt(d), float(p), hash_key(seed),
               _lib.stream())
     return out, lse
 
@@ -649,8 +650,8 @@ def attn_varlen_bwd(qkv, bqkv, seqs: PackedSeqs, out, lse, dout, dbqkv, heads, p
     dqkv = torch.empty_like(qkv)
     work = _lib.workspace(heads * T_ * 4, qkv.device, "attn_rowdot")  # D = rowsum(dO∘O) [heads, T]
     _lib.call("kfa_attn_causal_bwd" if causal else "kfa_attn_varlen_bwd", _lib.ptr(qkv), _lib.ptr(bqkv),
-              _lib.ptr(seqs.cu_dev), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(dout), _lib.ptr(dqkv), _lib.ptr(dbqkv), seqs.B, T_, seqs.max_seqlen, heads, 64,
-              1.0 / math.sqrt(64), float(p), hash_key(seed), _lib.ptr(work), _lib.stream())
+              _lib.ptr(seqs.cu_dev), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(dout), _lib.ptr(dqkv), _lib.ptr(dbqkv), seqs.B, T_, seqs.max_seqlen, heads, H // heads,
+              1.0 / math.sqrt(H // heads), float(p), hash_key(seed), _lib.ptr(work), _lib.stream())
     return dqkv
 
 
@@ -765,8 +766,8 @@ class EncoderLayerFn(torch.autograd.Function):
         if seqs is not None:
             if key_bias is not None:
                 raise ValueError("EncoderLayerFn: a packed batch has no padded keys; key_bias must be None")
-            if d != 64:
-                raise ValueError(f"EncoderLayerFn: packed attention needs head dim 64, got {d}")
+            if d not in (64, 128):
+                raise ValueError(f"EncoderLayerFn: packed attention needs head dim 64 or 128, got {d}")
         # attention
         qkv = mm(x, wqkv)                                                 # [T, 3H]
         if seqs is not None:

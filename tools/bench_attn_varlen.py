@@ -43,15 +43,53 @@ def alternate(sides, rounds, iters):
     return {k: (min(v), statistics.median(v)) for k, v in t.items()}
 
 
-def causal(rounds):
-    """--causal: one BERT-base-shaped layer (12 heads, dropout 0.1), the causal kernels against the
-    bidirectional varlen kernels on the SAME packed batch: 32 sequences of 1024 tokens, and
-    lengths uniform in [128, 1024]."""
+def head_dims(rounds):
+    """--head-dim 128: one layer's attention at H = 768, dropout 0.1: 6 heads of 128
+    (attention_d128.hip) against 12 heads of 64 on the SAME packed qkv (equal FLOPs), bidirectional
+    and causal: 32 sequences of 1024 tokens, and lengths uniform in [128, 1024]."""
     d = torch.device("cuda")
     g = torch.Generator().manual_seed(0)
     torch.manual_seed(0)
-    h, p, S = 12, 0.1, 1024
-    H = h * 64
+    H, p, S = 768, 0.1, 1024
+    for name, lens in (("32 x 1024", torch.full((32,), S)), ("32, uniform in [128, 1024]",
+                                                            torch.randint(128, S + 1, (32,), generator=g))):
+        rows = int(lens.sum())
+        seqs = T.PackedSeqs(torch.cat([torch.zeros(1, dtype=torch.long), lens.cumsum(0)]), rows, S, d)
+        qkv = torch.randn(rows, 3 * H, device=d).to(torch.bfloat16)
+        dout = torch.randn(rows, H, device=d).to(torch.bfloat16)
+        bqkv = torch.randn(3 * H, device=d) * 0.1
+
+        def fwd(h, c):
+            return T.attn_varlen_fwd(qkv, bqkv, seqs, h, p, 7, causal=c)
+
+        def both(h, c):
+            out, lse = fwd(h, c)
+            T.attn_varlen_bwd(qkv, bqkv, seqs, out, lse, dout, None, h, p, 7, causal=c)
+
+        sides = {}
+        for c in (False, True):
+            for hd in (64, 128):  # the default arguments bind this iteration's values
+                sides[("causal" if c else "bidir", hd, "fwd")] = lambda h=H // hd, c=c: fwd(h, c)
+                sides[("causal" if c else "bidir", hd, "fwd+bwd")] = lambda h=H // hd, c=c: both(h, c)
+        r = alternate(sides, rounds, 20)
+        print(f"attention, {name}: {rows} rows, H = {H}")
+        for (c, hd, k), (lo, med) in r.items():
+            print(f"  {c:6s} d = {hd:3d} {k:8s} min {lo * 1e3:7.1f} us  median {med * 1e3:7.1f} us", flush=True)
+        for c in ("bidir", "causal"):
+            for k in ("fwd", "fwd+bwd"):
+                print(f"  {c} {k}: d128 / d64 = {r[(c, 128, k)][0] / r[(c, 64, k)][0]:.3f} (min), "
+                      f"{r[(c, 128, k)][1] / r[(c, 64, k)][1]:.3f} (median)")
+
+
+def causal(rounds, hd=64):
+    """--causal: one BERT-base-shaped layer (H = 768: 12 heads of 64, or 6 of 128 with --head-dim 128;
+    dropout 0.1), the causal kernels against the bidirectional varlen kernels on the SAME packed
+    batch: 32 sequences of 1024 tokens, and lengths uniform in [128, 1024]."""
+    d = torch.device("cuda")
+    g = torch.Generator().manual_seed(0)
+    torch.manual_seed(0)
+    h, p, S = 768 // hd, 0.1, 1024
+    H = h * hd
     for name, lens in (("32 x 1024", torch.full((32,), S)), ("32, uniform in [128, 1024]",
                                                             torch.randint(128, S + 1, (32,), generator=g))):
         rows = int(lens.sum())
@@ -82,9 +120,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--causal", action="store_true", help="causal vs bidirectional varlen kernels at 1024 tokens")
+    ap.add_argument("--head-dim", type=int, default=64, choices=[64, 128],
+                    help="128: d = 128 (6 heads) against d = 64 (12 heads) at H = 768; with --causal: the head dim of "
+                         "that comparison")
     args = ap.parse_args()
     if args.causal:
-        return causal(args.rounds)
+        return causal(args.rounds, args.head_dim)
+    if args.head_dim == 128:
+        return head_dims(args.rounds)
     d = torch.device("cuda")
     g = torch.Generator().manual_seed(0)
     torch.manual_seed(0)

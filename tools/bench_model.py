@@ -26,11 +26,11 @@ from kubeflow_controller_amd.trainer.engine import Engine, init_distributed, tim
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--model", default="bert_base", choices=["bert_base", "bert_large", "bert_tiny", "gpt_small",
-                                                             "gpt_tiny", "wide_deep", "wide_deep_tiny"])
+                                                             "gpt_xl", "gpt_tiny", "wide_deep", "wide_deep_tiny"])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 64; gpt: 8)")
-    ap.add_argument("--seq", type=int, default=None, help="sequence length (default 128; gpt: 1024, the longest "
+    ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 64; gpt: 8, gpt_xl: 4)")
+    ap.add_argument("--seq", type=int, default=None, help="sequence length (default 128; gpt_small: 1024, gpt_xl: 2048, the longest "
                     "document of a packed batch of batch * seq token rows)")
     ap.add_argument("--min-seq", type=int, default=128, help="gpt: the shortest document")
     ap.add_argument("--lr", type=float, default=1e-4)
@@ -42,8 +42,9 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     gpt = args.model.startswith("gpt")
     # gpt_small: 8 x 1024 = 8192 rows keeps the bf16 logits and their gradient (rows x 50304 each) at 0.8 GB apiece
-    args.batch = args.batch if args.batch is not None else (8 if gpt else 64)
-    args.seq = args.seq if args.seq is not None else (1024 if args.model == "gpt_small" else 128)
+    # gpt_xl: the same 8192-row budget as 4 x 2048 (its max_position), so the logits cost what gpt_small's do
+    args.batch = args.batch if args.batch is not None else ((4 if args.model == "gpt_xl" else 8) if gpt else 64)
+    args.seq = args.seq if args.seq is not None else {"gpt_small": 1024, "gpt_xl": 2048}.get(args.model, 128)
     info = init_distributed()
     if info.device.type != "cuda":
         raise SystemExit("bench_model.py needs an MI355X")
@@ -59,7 +60,7 @@ def main(argv=None) -> int:
         metric = f"{args.model} pre-training sequences/sec (seq {args.seq}, whole node)"
     elif gpt:
         from kubeflow_controller_amd.models.gpt import GptConfig, GptLM, flops_per_step, gpt_loss, synthetic_lm_batch
-        cfg = GptConfig.small() if args.model == "gpt_small" else GptConfig.tiny()
+        cfg = {"gpt_small": GptConfig.small, "gpt_xl": GptConfig.xl, "gpt_tiny": GptConfig.tiny}[args.model]()
         model = GptLM(cfg)
         batch = synthetic_lm_batch(cfg, args.batch * args.seq, args.seq, min(args.min_seq, args.seq), g, info.device)
         cu = batch[2].cu_host
