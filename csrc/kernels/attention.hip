@@ -2218,11 +2218,12 @@ KFA_API int kfa_attn_bwd(const void* qkv, const float* bqkv, const float* key_bi
 // attention_d128.hip (same contracts, same arguments).
 long kfa_attn_d128_blocks(int B, int max_seqlen, int heads);
 int kfa_attn_d128_fwd(bool causal, const void* qkv, const float* bqkv, const int* cu, void* out, float* lse, int B,
-                      int T, int max_seqlen, int heads, float qscale, uint32_t th, float ds, uint64_t seed,
-                      hipStream_t st);
+                      int T, int max_seqlen, int heads, int kv_heads, float qscale, uint32_t th, float ds,
+                      uint64_t seed, hipStream_t st);
 int kfa_attn_d128_bwd(bool causal, const void* qkv, const float* bqkv, const int* cu, const void* out,
                       const float* lse, const void* dout, void* dqkv, float* dbqkv, int B, int T, int max_seqlen,
-                      int heads, float qscale, uint32_t th, float ds, uint64_t seed, float* work, hipStream_t st);
+                      int heads, int kv_heads, float qscale, uint32_t th, float ds, uint64_t seed, float* work,
+                      hipStream_t st);
 static bool attn_varlen_args_ok(int B, int T, int max_seqlen, int heads, int d) {
   if (B <= 0 || T <= 0 || heads <= 0 || (d != AD && d != 128) || max_seqlen < 1 || max_seqlen > 8192) return false;
   if (d == 128) return kfa_attn_d128_blocks(B, max_seqlen, heads) < (1L << 31);
@@ -2235,7 +2236,7 @@ KFA_API int kfa_attn_varlen_fwd(const void* qkv, const float* bqkv, const int* c
   if (!qkv || !bqkv || !cu || !out || !lse || !attn_varlen_args_ok(B, T, max_seqlen, heads, d)) return -1;
   const uint32_t th = attn_drop_t16(p);
   if (d == 128)
-    return kfa_attn_d128_fwd(false, qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, qscale, th, attn_drop_scale(th),
+    return kfa_attn_d128_fwd(false, qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, heads, qscale, th, attn_drop_scale(th),
                              (uint64_t)seed, st);
   const dim3 grid((unsigned)((long)B * heads * ((max_seqlen + BLK - 1) / BLK)));
   hipLaunchKernelGGL(attn_varlen_fwd_kernel, grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu, (bf16_t*)out, lse, B,
@@ -2254,7 +2255,7 @@ KFA_API int kfa_attn_varlen_bwd(const void* qkv, const float* bqkv, const int* c
   const uint32_t th = attn_drop_t16(p);
   const float ds = attn_drop_scale(th);
   if (d == 128)
-    return kfa_attn_d128_bwd(false, qkv, bqkv, cu, out, lse, dout, dqkv, dbqkv, B, T, max_seqlen, heads, qscale, th, ds,
+    return kfa_attn_d128_bwd(false, qkv, bqkv, cu, out, lse, dout, dqkv, dbqkv, B, T, max_seqlen, heads, heads, qscale, th, ds,
                              (uint64_t)seed, work, st);
   hipLaunchKernelGGL(attn_varlen_rowdot_kernel, dim3((unsigned)(((long)T * heads + 255) / 256)), dim3(256), 0, st,
                      (const bf16_t*)dout, (const bf16_t*)out, cu, work, B, T, heads);
@@ -2278,7 +2279,7 @@ KFA_API int kfa_attn_causal_fwd(const void* qkv, const float* bqkv, const int* c
   if (!qkv || !bqkv || !cu || !out || !lse || !attn_varlen_args_ok(B, T, max_seqlen, heads, d)) return -1;
   const uint32_t th = attn_drop_t16(p);
   if (d == 128)
-    return kfa_attn_d128_fwd(true, qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, qscale, th, attn_drop_scale(th),
+    return kfa_attn_d128_fwd(true, qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, heads, qscale, th, attn_drop_scale(th),
                              (uint64_t)seed, st);
   hipLaunchKernelGGL(attn_causal_fwd_kernel, dim3(attn_causal_grid(B, max_seqlen, heads)), dim3(256), 0, st,
                      (const bf16_t*)qkv, bqkv, cu, (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th,
@@ -2295,7 +2296,7 @@ KFA_API int kfa_attn_causal_bwd(const void* qkv, const float* bqkv, const int* c
   const uint32_t th = attn_drop_t16(p);
   const float ds = attn_drop_scale(th);
   if (d == 128)
-    return kfa_attn_d128_bwd(true, qkv, bqkv, cu, out, lse, dout, dqkv, dbqkv, B, T, max_seqlen, heads, qscale, th, ds,
+    return kfa_attn_d128_bwd(true, qkv, bqkv, cu, out, lse, dout, dqkv, dbqkv, B, T, max_seqlen, heads, heads, qscale, th, ds,
                              (uint64_t)seed, work, st);
   hipLaunchKernelGGL(attn_varlen_rowdot_kernel, dim3((unsigned)(((long)T * heads + 255) / 256)), dim3(256), 0, st,
                      (const bf16_t*)dout, (const bf16_t*)out, cu, work, B, T, heads);
@@ -2305,4 +2306,35 @@ KFA_API int kfa_attn_causal_bwd(const void* qkv, const float* bqkv, const int* c
   hipLaunchKernelGGL(attn_causal_bwd_q_kernel, grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu, lse, work,
                      (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th, ds, (uint64_t)seed);
   return kfa_status();
+}
+
+// Grouped-query attention over a packed batch, head dim 128 only (attention_d128.hip): qkv
+// [T, (heads + 2·kv_heads)·128] = Q heads | K heads | V heads, query head h reads KV head
+// h / (heads / kv_heads); out [T, heads·128], lse [heads, T]; bqkv / dbqkv [(heads + 2·kv_heads)·128].
+// Everything else is the contract of kfa_attn_varlen_* (causal: of kfa_attn_causal_*).
+static bool attn_gqa_args_ok(int B, int T, int max_seqlen, int heads, int kv_heads, int d) {
+  if (d != 128 || kv_heads < 1 || heads < kv_heads || heads % kv_heads) return false;
+  return attn_varlen_args_ok(B, T, max_seqlen, heads, d);  // the query-head grids are the largest
+}
+
+KFA_API int kfa_attn_gqa_fwd(const void* qkv, const float* bqkv, const int* cu, void* out, float* lse, int B, int T,
+                             int max_seqlen, int heads, int kv_heads, int d, int causal, float qscale, float p,
+                             unsigned long long seed, hipStream_t st) {
+  if (!qkv || !bqkv || !cu || !out || !lse || !attn_gqa_args_ok(B, T, max_seqlen, heads, kv_heads, d)) return -1;
+  const uint32_t th = attn_drop_t16(p);
+  return kfa_attn_d128_fwd(causal != 0, qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, kv_heads, qscale, th,
+                           attn_drop_scale(th), (uint64_t)seed, st);
+}
+
+KFA_API int kfa_attn_gqa_bwd(const void* qkv, const float* bqkv, const int* cu, const void* out, const float* lse,
+                             const void* dout, void* dqkv, float* dbqkv, int B, int T, int max_seqlen, int heads,
+                             int kv_heads, int d, int causal, float qscale, float p, unsigned long long seed,
+                             float* work, hipStream_t st) {
+  if (!qkv || !bqkv || !cu || !out || !lse || !dout || !dqkv ||
+      !attn_gqa_args_ok(B, T, max_seqlen, heads, kv_heads, d))
+    return -1;
+  if (!work) return -3;
+  const uint32_t th = attn_drop_t16(p);
+  return kfa_attn_d128_bwd(causal != 0, qkv, bqkv, cu, out, lse, dout, dqkv, dbqkv, B, T, max_seqlen, heads, kv_heads,
+                           qscale, th, attn_drop_scale(th), (uint64_t)seed, work, st);
 }

@@ -51,6 +51,19 @@
 //   no MFMA is issued for a 16-key score tile, a 32-key P·V / dQ slice or a 32-query
 //   dK / dV step wholly past len or wholly past the wave's diagonal bound; only tiles
 //   the diagonal crosses select on key > query.
+// Grouped-query attention (the GQA = true instances; kv_heads K / V heads for `heads`
+//   query heads, g = heads / kv_heads, qkv [T, (heads + 2·kv_heads)·128] = Q | K | V).
+//   Forward and dQ keep the work split above; only the streamed K / V images come from
+//   head h / g at the narrower row stride, both scalar.  dK / dV is owned by the KV
+//   head: one workgroup per (sequence, KV head, 64-key block) keeps its keys' K and V in
+//   registers and streams the Q / dO blocks of its g query heads one after the other
+//   in ONE flattened loop (still one image load and two barriers per streamed block),
+//   taking lse, D, the Q / dO columns and the dropout hash row from the current query
+//   head.  dK / dV accumulate in the same registers over the whole group and are stored
+//   once: no atomics, no fp32 scratch, no second pass, bit-repeatable.  (A workgroup per
+//   query head would need g-way fp32 atomics into a scratch and a convert pass.)  The
+//   GQA = false instances compile to the instructions they had before the template
+//   argument existed; their trailing kv_heads argument is not read.
 #include "attn_tile.h"
 
 namespace {
@@ -192,14 +205,24 @@ __device__ __forceinline__ bool own_block(const int* __restrict__ cu, int B, int
   return w.blk * OB < w.len;
 }
 
+// Grouped-query attention (GQA instances): qkv rows hold `heads` query heads, then kv_heads K heads,
+// then kv_heads V heads; query head h reads KV head h / g, g = heads / kv_heads.  The row width and
+// the K / V columns are uniform over the workgroup (scalar registers).  Multi-head instances
+// (GQA = false) ignore kv_heads.
+template <bool GQA>
+__device__ __forceinline__ int kv_head(int h, int heads, int kv_heads) {
+  if constexpr (GQA) return h / (heads / kv_heads);
+  return h;
+}
+
 // forward: workgroup per (sequence, head, block of 64·RT queries); wave w owns queries 16·RT·w.. as
 // register operands, streams 64-key blocks (K, V images), online softmax per block, P feeds P·V
 // from registers
-template <int RT, bool CAUSAL>
+template <int RT, bool CAUSAL, bool GQA>
 __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_fwd_kernel(
     const bf16_t* __restrict__ qkv, const float* __restrict__ bqkv, const int* __restrict__ cu,
     bf16_t* __restrict__ out, float* __restrict__ lse, int B, int T, int heads, int max_seqlen, float qscale,
-    uint32_t thresh, float dscale, uint64_t seed) {
+    uint32_t thresh, float dscale, uint64_t seed, int kv_heads) {
   constexpr int OB = 64 * RT, WR = 16 * RT;
   __shared__ __attribute__((aligned(16))) char sm[2 * IMG];  // K, V images (32 KiB)
   char* Ki = sm;
@@ -208,7 +231,8 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_fwd_kernel(
   OwnBlock w;
   if (!own_block<OB, CAUSAL, true>(cu, B, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
   const int h = w.h, H = heads * HD;
-  const long W3 = 3L * H, q0 = (long)w.s0 + (long)w.blk * OB;
+  const int hk = kv_head<GQA>(h, heads, kv_heads), VC = GQA ? H + kv_heads * HD : 2 * H;  // KV head, V's first column
+  const long W3 = GQA ? (long)H + 2L * kv_heads * HD : 3L * H, q0 = (long)w.s0 + (long)w.blk * OB;
   if (w.blk == 0 && w.b == B - 1) zero_rows_d(out, H, h * HD, (long)w.s0 + w.len, T, tid);
   const int qlive = min(OB, w.len - w.blk * OB);
   const int qb = wave * WR, qabs = w.blk * OB + qb;  // the wave's first query: in the block, in the sequence
@@ -239,7 +263,7 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_fwd_kernel(
     const int klive = min(SB, w.len - j * SB);  // >= 1
     if (j > 0) __syncthreads();                 // every wave is done with key block j-1
     {
-      const int col[2] = {H + h * HD, 2 * H + h * HD};
+      const int col[2] = {H + hk * HD, VC + hk * HD};
       const bool tf[2] = {true, true};
       const float sc[2] = {1.f, 1.f};
       char* const img[2] = {Ki, Vi};
@@ -397,25 +421,27 @@ __global__ KFA_NO_PK_F32 void attn_d128_rowdot_kernel(const bf16_t* __restrict__
 
 // key-owner dK / dV: workgroup per (sequence, head, block of 64·RT keys); wave w owns keys 16·RT·w..
 // (K and V rows as register operands) and streams 64-query blocks (Q, dO images); causal: from the
-// query block that holds its first key on
-template <int RT, bool CAUSAL>
+// query block that holds its first key on.  GQA: the owner is a KV head and the Q / dO blocks of
+// its g query heads stream past the same K / V registers and accumulators
+template <int RT, bool CAUSAL, bool GQA>
 __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_kv_kernel(
     const bf16_t* __restrict__ qkv, const float* __restrict__ bqkv, const int* __restrict__ cu,
     const float* __restrict__ lse, const float* __restrict__ Dq, const bf16_t* __restrict__ dout,
     bf16_t* __restrict__ dqkv, float* __restrict__ dbqkv, int B, int T, int heads, int max_seqlen, float qscale,
-    uint32_t thresh, float dscale, uint64_t seed) {
+    uint32_t thresh, float dscale, uint64_t seed, int kv_heads) {
   constexpr int OB = 64 * RT, WR = 16 * RT;
   __shared__ __attribute__((aligned(16))) char sm[2 * IMG];  // Q, dO images (32 KiB)
   char* Qi = sm;
   char* Gi = sm + IMG;
   const int tid = threadIdx.x, lane0 = tid & 63, wave = tid >> 6, fr0 = lane0 & 15, fq0 = lane0 >> 4;
   OwnBlock w;
-  if (!own_block<OB, CAUSAL, false>(cu, B, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
-  const int h = w.h, H = heads * HD;
-  const long W3 = 3L * H, k0 = (long)w.s0 + (long)w.blk * OB;
+  // GQA: the owner is a KV head; w.h counts KV heads and the query heads w.h·g .. w.h·g + g-1 stream past it
+  if (!own_block<OB, CAUSAL, false>(cu, B, T, GQA ? kv_heads : heads, max_seqlen, w)) return;  // uniform, before any barrier
+  const int hk = w.h, H = heads * HD, g = GQA ? heads / kv_heads : 1, VC = GQA ? H + kv_heads * HD : 2 * H;
+  const long W3 = GQA ? (long)H + 2L * kv_heads * HD : 3L * H, k0 = (long)w.s0 + (long)w.blk * OB;
   if (w.blk == 0 && w.b == B - 1) {
-    zero_rows_d(dqkv, W3, H + h * HD, (long)w.s0 + w.len, T, tid);
-    zero_rows_d(dqkv, W3, 2 * H + h * HD, (long)w.s0 + w.len, T, tid);
+    zero_rows_d(dqkv, W3, H + hk * HD, (long)w.s0 + w.len, T, tid);
+    zero_rows_d(dqkv, W3, VC + hk * HD, (long)w.s0 + w.len, T, tid);
   }
   const int klive = min(OB, w.len - w.blk * OB), nqb = (w.len + SB - 1) / SB;
   const int kw = wave * WR, kabs = w.blk * OB + kw;  // the wave's first key: in the block, in the sequence
@@ -429,9 +455,9 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_kv_kernel(
     if (wlive) {
 #pragma unroll
       for (int ks = 0; ks < 4; ks++) {
-        const int c = h * HD + ks * 32 + fq0 * 8;
+        const int c = hk * HD + ks * 32 + fq0 * 8;
         kreg[kt][ks] = row_operand<true>(qkv + (k0 + row) * W3 + H + c, keyok[kt], bqkv + H + c, 1.f);
-        vreg[kt][ks] = row_operand<true>(qkv + (k0 + row) * W3 + 2 * H + c, keyok[kt], bqkv + 2 * H + c, 1.f);
+        vreg[kt][ks] = row_operand<true>(qkv + (k0 + row) * W3 + VC + c, keyok[kt], bqkv + VC + c, 1.f);
       }
     }
   }
@@ -441,10 +467,22 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_kv_kernel(
 #pragma unroll
     for (int kt = 0; kt < RT; kt++) dvT[dt][kt] = dkT[dt][kt] = floatx4{0.f, 0.f, 0.f, 0.f};
   const int i0 = CAUSAL ? (w.blk * OB) / SB : 0;  // the loop bound is the causal mask above the diagonal
-  for (int i = i0; i < nqb; i++) {
+  // one flattened loop over (query head of the group, query block): the accumulators, the barriers
+  // and the image loads do not know where one query head ends and the next begins
+  const int nq = nqb - i0;       // query blocks streamed per query head
+  int h = hk * g, wrap = nqb;    // the streamed block's query head; the counter at which the next one begins
+  for (int u = i0; u < i0 + nq * g; u++) {
+    int i = u;  // the streamed query block
+    if constexpr (GQA) {
+      if (u == wrap) {
+        wrap += nq;
+        h++;
+      }
+      i = u - (wrap - nqb);
+    }
     const int qlive = min(SB, w.len - i * SB);
     const long qrow0 = (long)w.s0 + (long)i * SB;
-    if (i > i0) __syncthreads();  // every wave is done with the previous Q / dO images
+    if (u > i0) __syncthreads();  // every wave is done with the previous Q / dO images
     {
       const int col[2] = {h * HD, h * HD};
       const bool tf[2] = {true, false};
@@ -544,19 +582,19 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_kv_kernel(
   stage_tile_d<RT>(st, dkT, 1.f, fr0, fq0);
   stage_tile_d<RT>(st + WR * HD * 2, dvT, 1.f, fr0, fq0);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  store_tile_d<RT>(st, dqkv, k0 + kw, W3, H + h * HD, klive - kw, dbqkv, lane0);
-  store_tile_d<RT>(st + WR * HD * 2, dqkv, k0 + kw, W3, 2 * H + h * HD, klive - kw, dbqkv, lane0);
+  store_tile_d<RT>(st, dqkv, k0 + kw, W3, H + hk * HD, klive - kw, dbqkv, lane0);
+  store_tile_d<RT>(st + WR * HD * 2, dqkv, k0 + kw, W3, VC + hk * HD, klive - kw, dbqkv, lane0);
 }
 
 // query-owner dQ = dS·K: workgroup per (sequence, head, block of 64·RT queries); wave w owns queries
 // 16·RT·w.. (Q and dO rows as register operands) and streams 64-key blocks (K, V images), one 32-key
 // slice (a dropout hash pair and one dQ k-step) at a time
-template <int RT, bool CAUSAL>
+template <int RT, bool CAUSAL, bool GQA>
 __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_q_kernel(
     const bf16_t* __restrict__ qkv, const float* __restrict__ bqkv, const int* __restrict__ cu,
     const float* __restrict__ lse, const float* __restrict__ Dq, const bf16_t* __restrict__ dout,
     bf16_t* __restrict__ dqkv, float* __restrict__ dbqkv, int B, int T, int heads, int max_seqlen, float qscale,
-    uint32_t thresh, float dscale, uint64_t seed) {
+    uint32_t thresh, float dscale, uint64_t seed, int kv_heads) {
   constexpr int OB = 64 * RT, WR = 16 * RT;
   __shared__ __attribute__((aligned(16))) char sm[2 * IMG];  // K, V images (32 KiB)
   char* Ki = sm;
@@ -565,7 +603,8 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_q_kernel(
   OwnBlock w;
   if (!own_block<OB, CAUSAL, true>(cu, B, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
   const int h = w.h, H = heads * HD;
-  const long W3 = 3L * H, q0 = (long)w.s0 + (long)w.blk * OB;
+  const int hk = kv_head<GQA>(h, heads, kv_heads), VC = GQA ? H + kv_heads * HD : 2 * H;  // KV head, V's first column
+  const long W3 = GQA ? (long)H + 2L * kv_heads * HD : 3L * H, q0 = (long)w.s0 + (long)w.blk * OB;
   if (w.blk == 0 && w.b == B - 1) zero_rows_d(dqkv, W3, h * HD, (long)w.s0 + w.len, T, tid);
   const int qlive = min(OB, w.len - w.blk * OB);
   const int qb = wave * WR, qabs = w.blk * OB + qb;
@@ -601,7 +640,7 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_q_kernel(
     const int klive = min(SB, w.len - j * SB);
     if (j > 0) __syncthreads();  // every wave is done with key block j-1
     {
-      const int col[2] = {H + h * HD, 2 * H + h * HD};
+      const int col[2] = {H + hk * HD, VC + hk * HD};
       const bool tf[2] = {true, true};
       const float sc[2] = {1.f, 1.f};
       char* const img[2] = {Ki, Vi};
@@ -679,49 +718,74 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_q_kernel(
 // 16-row tiles per wave: owner blocks of 128 queries (forward, dQ) and of 64 keys (dK / dV)
 constexpr int FWD_RT = 2, DQ_RT = 2, KV_RT = 1;
 
+template <bool CAUSAL>
+void launch_fwd(const void* qkv, const float* bqkv, const int* cu, void* out, float* lse, int B, int T, int max_seqlen,
+                int heads, int kv_heads, float qscale, uint32_t th, float ds, uint64_t seed, hipStream_t st) {
+  const dim3 grid((unsigned)((long)B * heads * ((max_seqlen + 64 * FWD_RT - 1) / (64 * FWD_RT))));
+  if (kv_heads == heads)
+    hipLaunchKernelGGL((attn_d128_fwd_kernel<FWD_RT, CAUSAL, false>), grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
+                       cu, (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th, ds, seed, kv_heads);
+  else
+    hipLaunchKernelGGL((attn_d128_fwd_kernel<FWD_RT, CAUSAL, true>), grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
+                       cu, (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th, ds, seed, kv_heads);
+}
+
+// dK / dV then dQ.  GQA: the dK / dV grid is over KV heads, a workgroup does its group's g query heads
+template <bool CAUSAL>
+void launch_bwd(const void* qkv, const float* bqkv, const int* cu, const float* lse, const float* work,
+                const void* dout, void* dqkv, float* dbqkv, int B, int T, int max_seqlen, int heads, int kv_heads,
+                float qscale, uint32_t th, float ds, uint64_t seed, hipStream_t st) {
+  const dim3 gkv((unsigned)((long)B * kv_heads * ((max_seqlen + 64 * KV_RT - 1) / (64 * KV_RT))));
+  const dim3 gq((unsigned)((long)B * heads * ((max_seqlen + 64 * DQ_RT - 1) / (64 * DQ_RT))));
+  if (kv_heads == heads) {
+    hipLaunchKernelGGL((attn_d128_bwd_kv_kernel<KV_RT, CAUSAL, false>), gkv, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
+                       cu, lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th,
+                       ds, seed, kv_heads);
+    hipLaunchKernelGGL((attn_d128_bwd_q_kernel<DQ_RT, CAUSAL, false>), gq, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
+                       cu, lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th,
+                       ds, seed, kv_heads);
+  } else {
+    hipLaunchKernelGGL((attn_d128_bwd_kv_kernel<KV_RT, CAUSAL, true>), gkv, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
+                       cu, lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th,
+                       ds, seed, kv_heads);
+    hipLaunchKernelGGL((attn_d128_bwd_q_kernel<DQ_RT, CAUSAL, true>), gq, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
+                       cu, lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th,
+                       ds, seed, kv_heads);
+  }
+}
+
 }  // namespace
 
-// blocks of the largest d = 128 grid (attention.hip's entry points check it against 2^31)
-static long d128_blocks(int B, int max_seqlen, int heads, int rt) {
-  return (long)B * heads * ((max_seqlen + 64 * rt - 1) / (64 * rt));
+// blocks of the largest d = 128 grid (attention.hip's entry points check it against 2^31): the
+// 64-key dK / dV blocks of `heads` heads, which is also above the 128-query grids of a GQA launch
+long kfa_attn_d128_blocks(int B, int max_seqlen, int heads) {
+  return (long)B * heads * ((max_seqlen + 64 * KV_RT - 1) / (64 * KV_RT));
 }
-long kfa_attn_d128_blocks(int B, int max_seqlen, int heads) { return d128_blocks(B, max_seqlen, heads, KV_RT); }
 
-// The d = 128 side of kfa_attn_varlen_fwd / kfa_attn_causal_fwd: arguments already checked there
+// The d = 128 side of kfa_attn_varlen_fwd / kfa_attn_causal_fwd / kfa_attn_gqa_fwd: arguments already
+// checked there; kv_heads == heads: the multi-head kernels
 int kfa_attn_d128_fwd(bool causal, const void* qkv, const float* bqkv, const int* cu, void* out, float* lse, int B,
-                      int T, int max_seqlen, int heads, float qscale, uint32_t th, float ds, uint64_t seed,
-                      hipStream_t st) {
-  const dim3 grid((unsigned)d128_blocks(B, max_seqlen, heads, FWD_RT));
+                      int T, int max_seqlen, int heads, int kv_heads, float qscale, uint32_t th, float ds,
+                      uint64_t seed, hipStream_t st) {
   if (causal)
-    hipLaunchKernelGGL((attn_d128_fwd_kernel<FWD_RT, true>), grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu,
-                       (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th, ds, seed);
+    launch_fwd<true>(qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, kv_heads, qscale, th, ds, seed, st);
   else
-    hipLaunchKernelGGL((attn_d128_fwd_kernel<FWD_RT, false>), grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu,
-                       (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th, ds, seed);
+    launch_fwd<false>(qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, kv_heads, qscale, th, ds, seed, st);
   return kfa_status();
 }
 
-// The d = 128 side of kfa_attn_varlen_bwd / kfa_attn_causal_bwd; work: heads·T floats
+// The d = 128 side of kfa_attn_varlen_bwd / kfa_attn_causal_bwd / kfa_attn_gqa_bwd; work: heads·T floats
 int kfa_attn_d128_bwd(bool causal, const void* qkv, const float* bqkv, const int* cu, const void* out,
                       const float* lse, const void* dout, void* dqkv, float* dbqkv, int B, int T, int max_seqlen,
-                      int heads, float qscale, uint32_t th, float ds, uint64_t seed, float* work, hipStream_t st) {
+                      int heads, int kv_heads, float qscale, uint32_t th, float ds, uint64_t seed, float* work,
+                      hipStream_t st) {
   hipLaunchKernelGGL(attn_d128_rowdot_kernel, dim3((unsigned)(((long)T * heads + 255) / 256)), dim3(256), 0, st,
                      (const bf16_t*)dout, (const bf16_t*)out, cu, work, B, T, heads);
-  const dim3 gkv((unsigned)d128_blocks(B, max_seqlen, heads, KV_RT)), gq((unsigned)d128_blocks(B, max_seqlen, heads, DQ_RT));
-  if (causal) {
-    hipLaunchKernelGGL((attn_d128_bwd_kv_kernel<KV_RT, true>), gkv, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu,
-                       lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th, ds,
-                       seed);
-    hipLaunchKernelGGL((attn_d128_bwd_q_kernel<DQ_RT, true>), gq, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu,
-                       lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th, ds,
-                       seed);
-  } else {
-    hipLaunchKernelGGL((attn_d128_bwd_kv_kernel<KV_RT, false>), gkv, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu,
-                       lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th, ds,
-                       seed);
-    hipLaunchKernelGGL((attn_d128_bwd_q_kernel<DQ_RT, false>), gq, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu,
-                       lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th, ds,
-                       seed);
-  }
+  if (causal)
+    launch_bwd<true>(qkv, bqkv, cu, lse, work, dout, dqkv, dbqkv, B, T, max_seqlen, heads, kv_heads, qscale, th, ds,
+                     seed, st);
+  else
+    launch_bwd<false>(qkv, bqkv, cu, lse, work, dout, dqkv, dbqkv, B, T, max_seqlen, heads, kv_heads, qscale, th, ds,
+                      seed, st);
   return kfa_status();
 }

@@ -66,8 +66,11 @@ class BertLayer(nn.Module):
     def __init__(self, cfg: BertConfig):
         super().__init__()
         H, I = cfg.hidden, cfg.intermediate
-        self.wqkv = nn.Parameter(torch.empty(3 * H, H))
-        self.bqkv = nn.Parameter(torch.zeros(3 * H))
+        # grouped-query attention (a config with kv_heads): kv_heads K and V heads after the query heads
+        kv_heads = getattr(cfg, "kv_heads", None)
+        W = 3 * H if kv_heads is None else H + 2 * kv_heads * (H // cfg.heads)
+        self.wqkv = nn.Parameter(torch.empty(W, H))
+        self.bqkv = nn.Parameter(torch.zeros(W))
         self.wo = nn.Parameter(torch.empty(H, H))
         self.bo = nn.Parameter(torch.zeros(H))
         self.ln1_g = nn.Parameter(torch.ones(H))

@@ -23,6 +23,7 @@ CPU path: the same parameters through plain PyTorch fp32 ops (no dropout).
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -44,6 +45,7 @@ class GptConfig:
     attn_dropout: float = 0.1
     ln_eps: float = 1e-5
     init_range: float = 0.02
+    kv_heads: Optional[int] = None  # grouped-query attention: K / V heads (divides heads; head dim 128 only)
 
     @classmethod
     def small(cls) -> "GptConfig":
@@ -55,6 +57,12 @@ class GptConfig:
         1.32 B parameters (24 x 50.4 M of layers + 103 M of tied token and 4 M of position
         embeddings)."""
         return cls(hidden=2048, layers=24, heads=16, intermediate=8192, max_position=2048)
+
+    @classmethod
+    def xl_gqa(cls) -> "GptConfig":
+        """The ``xl`` shape with grouped-query attention: 16 query heads share 4 K / V heads of 128
+        (the QKV projection is [3072, 2048] instead of [6144, 2048])."""
+        return cls(hidden=2048, layers=24, heads=16, kv_heads=4, intermediate=8192, max_position=2048)
 
     @classmethod
     def tiny(cls) -> "GptConfig":
@@ -81,6 +89,12 @@ class GptLM(nn.Module):
         super().__init__()
         self.cfg = cfg
         H, V = cfg.hidden, cfg.padded_vocab
+        if cfg.kv_heads is not None:
+            if cfg.kv_heads < 1 or cfg.heads % cfg.kv_heads:
+                raise ValueError(f"GptLM: kv_heads must divide heads (heads={cfg.heads}, kv_heads={cfg.kv_heads})")
+            if H != cfg.heads * 128:
+                raise ValueError(f"GptLM: grouped-query attention needs head dim 128, got {H / cfg.heads:g} "
+                                 f"(hidden={H}, heads={cfg.heads})")
         self.word_emb = nn.Parameter(torch.empty(V, H))
         self.pos_emb = nn.Parameter(torch.empty(cfg.max_position, H))
         for w in (self.word_emb, self.pos_emb):
@@ -121,7 +135,7 @@ class GptLM(nn.Module):
         for i, layer in enumerate(self.layers):
             join_out = T.ResidualJoin() if (self.training and i + 1 < len(self.layers)) else None
             lcfg = (seqs.B, seqs.max_seqlen, cfg.heads, ph, pa, T.s64(T.mix_seed(step_seed, i)), cfg.ln_eps, join_in,
-                    join_out, seqs, True)
+                    join_out, seqs, True, cfg.kv_heads)
             h = T.EncoderLayerFn.apply(h, None, lcfg, *layer.params())
             join_in = join_out
         # decoder_xent means over all rows (ignored rows add 0): rescale to the rows with a
@@ -136,7 +150,7 @@ class GptLM(nn.Module):
         cfg = self.cfg
         f = lambda t: t.float()  # noqa: E731
         h = f(self.word_emb)[input_ids.reshape(-1)] + f(self.pos_emb)[position_ids.reshape(-1)]
-        lcfg = (seqs.B, seqs.max_seqlen, cfg.heads, 0.0, 0.0, 0, cfg.ln_eps, None, None, seqs, True)
+        lcfg = (seqs.B, seqs.max_seqlen, cfg.heads, 0.0, 0.0, 0, cfg.ln_eps, None, None, seqs, True, cfg.kv_heads)
         for layer in self.layers:
             h = T.encoder_layer_reference(h, None, lcfg, *layer.params())
         logits = h @ f(self.word_emb).t() + f(self.dec_b)
@@ -173,9 +187,11 @@ def synthetic_lm_batch(cfg: GptConfig, rows: int, seq_len: int, min_len: int, ge
 
 def flops_per_step(cfg: GptConfig, lens) -> float:
     """Model FLOPs (fwd+bwd = 3x fwd) of one step on sequences of ``lens`` tokens; attention
-    counts the visible half of each score matrix."""
+    counts the visible half of each score matrix; with ``kv_heads`` the QKV projection is
+    ``(heads + 2·kv_heads)·d`` wide."""
     Tk = float(sum(lens))
     H, I, L = cfg.hidden, cfg.intermediate, cfg.layers
     attn = sum(2 * 2 * (n * (n + 1) / 2) * H for n in lens)
-    per_layer = 2 * Tk * (3 * H * H + H * H + 2 * H * I) + attn
+    Wqkv = 3 * H if cfg.kv_heads is None else H + 2 * cfg.kv_heads * (H // cfg.heads)
+    per_layer = 2 * Tk * (Wqkv * H + H * H + 2 * H * I) + attn
     return 3.0 * (L * per_layer + 2 * Tk * H * cfg.padded_vocab)

@@ -64,6 +64,8 @@ _lib.register("kfa_attn_varlen_fwd", [P, P, P, P, P, I, I, I, I, I, Fl, Fl, U64,
 _lib.register("kfa_attn_varlen_bwd", [P, P, P, P, P, P, P, P, I, I, I, I, I, Fl, Fl, U64, P, P])
 _lib.register("kfa_attn_causal_fwd", [P, P, P, P, P, I, I, I, I, I, Fl, Fl, U64, P])
 _lib.register("kfa_attn_causal_bwd", [P, P, P, P, P, P, P, P, I, I, I, I, I, Fl, Fl, U64, P, P])
+_lib.register("kfa_attn_gqa_fwd", [P, P, P, P, P, I, I, I, I, I, I, I, Fl, Fl, U64, P])
+_lib.register("kfa_attn_gqa_bwd", [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, Fl, Fl, U64, P, P])
 
 # env KFA_FUSED_ATTN=0 falls back to the split kernels + batched library GEMMs
 FUSED_ATTN = os.environ.get("KFA_FUSED_ATTN", "1") != "0"
@@ -592,13 +594,33 @@ class PackedSeqs:
             raise ValueError(f"PackedSeqs: a sequence of {int(lens.max())} tokens exceeds max_seqlen {self.max_seqlen}")
 
 
-def _varlen_check(name, qkv, bqkv, seqs, heads):
+def _gqa(heads, kv_heads):
+    """kv_heads of a grouped-query call, None for multi-head attention (None or == heads)."""
+    return None if kv_heads is None or kv_heads == heads else kv_heads
+
+
+def _varlen_check(name, qkv, bqkv, seqs, heads, kv_heads=None):
     if not isinstance(seqs, PackedSeqs):
         raise ValueError(f"{name}: seqs must be a PackedSeqs")
     if qkv.dim() != 2 or qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
         raise ValueError(f"{name}: qkv must be a contiguous bf16 [T, 3H] tensor")
     T_, W3 = qkv.shape
-    if heads <= 0 or W3 % (3 * heads) or W3 // (3 * heads) not in (64, 128):
+    if _gqa(heads, kv_heads) is not None:
+        # grouped-query layout: [T, (heads + 2·kv_heads)·d], d = 128 only; every shape rule is
+        # checked before the device rule, so a CPU tensor reports the rule it breaks
+        if heads <= 0 or kv_heads < 1 or heads % kv_heads:
+            raise ValueError(f"{name}: kv_heads must divide heads (heads={heads}, kv_heads={kv_heads})")
+        nh = heads + 2 * kv_heads
+        if W3 % nh == 0 and W3 // nh == 64:
+            raise ValueError(f"{name}: grouped-query attention needs head dim 128 (qkv {tuple(qkv.shape)}, "
+                             f"heads={heads}, kv_heads={kv_heads}: head dim 64)")
+        if W3 != nh * 128:
+            raise ValueError(f"{name}: qkv must be [T, (heads + 2·kv_heads)·128] (qkv {tuple(qkv.shape)}, "
+                             f"heads={heads}, kv_heads={kv_heads})")
+        if bqkv is not None and (bqkv.dtype != torch.float32 or bqkv.numel() != W3 or not bqkv.is_contiguous()
+                                 or bqkv.device != qkv.device):
+            raise ValueError(f"{name}: bqkv must be a contiguous fp32 [(heads + 2·kv_heads)·128] vector")
+    elif heads <= 0 or W3 % (3 * heads) or W3 // (3 * heads) not in (64, 128):
         raise ValueError(f"{name}: head dim must be 64 or 128 (qkv {tuple(qkv.shape)}, heads={heads})")
     seqs.validate(T_)
     if not qkv.is_cuda or seqs.cu_dev.device != qkv.device:
@@ -611,14 +633,24 @@ def _varlen_check(name, qkv, bqkv, seqs, heads):
     return bqkv
 
 
-def attn_varlen_fwd(qkv, bqkv, seqs: PackedSeqs, heads, p=0.0, seed=0, causal=False):
+def attn_varlen_fwd(qkv, bqkv, seqs: PackedSeqs, heads, p=0.0, seed=0, causal=False, kv_heads=None):
     """(ctx [T, H], lse [heads, T]) of per-sequence softmax((q+b)(k+b)ᵀ/√d)·(v+b) over the
     packed batch ``seqs`` (``csrc/kernels/attention.hip``: attn_varlen_fwd_kernel; head dim
     128: ``attention_d128.hip``, same contracts); the unowned rows of ctx are zero.  Dropout: hash row ``h·T + token row``, key index
     within the sequence (attn_pair_hash with S = max_seqlen).  ``causal``: query i sees
-    keys 0..i of its sequence (attn_causal_fwd_kernel: the masked half is not computed)."""
-    bqkv = _varlen_check("attn_varlen_fwd", qkv, bqkv, seqs, heads)
+    keys 0..i of its sequence (attn_causal_fwd_kernel: the masked half is not computed).
+    ``kv_heads`` (other than None / ``heads``): grouped-query attention, head dim 128 only:
+    qkv [T, (heads + 2·kv_heads)·128] = Q heads | K heads | V heads, query head h reads KV
+    head ``h // (heads // kv_heads)``; ctx [T, heads·128]; the hash row is the query head's."""
+    bqkv = _varlen_check("attn_varlen_fwd", qkv, bqkv, seqs, heads, kv_heads)
     T_, W3 = qkv.shape
+    if _gqa(heads, kv_heads) is not None:
+        out = torch.empty(T_, heads * 128, dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty(heads, T_, dtype=torch.float32, device=qkv.device)
+        _lib.call("kfa_attn_gqa_fwd", _lib.ptr(qkv), _lib.ptr(bqkv), _lib.ptr(seqs.cu_dev), _lib.ptr(out),
+                  _lib.ptr(lse), seqs.B, T_, seqs.max_seqlen, heads, kv_heads, 128, int(bool(causal)),
+                  1.0 / math.sqrt(128), float(p), hash_key(seed), _lib.stream())
+        return out, lse
     H = W3 // 3
     d = H // heads
     out = torch.empty(T_, H, dtype=qkv.dtype, device=qkv.device)
@@ -629,13 +661,17 @@ def attn_varlen_fwd(qkv, bqkv, seqs: PackedSeqs, heads, p=0.0, seed=0, causal=Fa
     return out, lse
 
 
-def attn_varlen_bwd(qkv, bqkv, seqs: PackedSeqs, out, lse, dout, dbqkv, heads, p=0.0, seed=0, causal=False):
+def attn_varlen_bwd(qkv, bqkv, seqs: PackedSeqs, out, lse, dout, dbqkv, heads, p=0.0, seed=0, causal=False,
+                    kv_heads=None):
     """dqkv [T, 3H] of :func:`attn_varlen_fwd` (``out``, ``lse``: its outputs; unowned rows
     zero); the bias gradient is added into ``dbqkv`` (fp32 [3H], nullable).  ``causal`` as
-    the forward's (attn_causal_bwd_kv_kernel / attn_causal_bwd_q_kernel)."""
-    bqkv = _varlen_check("attn_varlen_bwd", qkv, bqkv, seqs, heads)
+    the forward's (attn_causal_bwd_kv_kernel / attn_causal_bwd_q_kernel).  ``kv_heads``: as the
+    forward's; dqkv and ``dbqkv`` have the grouped-query width, and a KV head's gradient is the
+    sum over its group's query heads, accumulated in registers by one workgroup."""
+    bqkv = _varlen_check("attn_varlen_bwd", qkv, bqkv, seqs, heads, kv_heads)
     T_, W3 = qkv.shape
-    H = W3 // 3
+    gqa = _gqa(heads, kv_heads) is not None
+    H = heads * 128 if gqa else W3 // 3
     dout = dout.contiguous()
     if tuple(dout.shape) != (T_, H) or dout.dtype != qkv.dtype or dout.device != qkv.device:
         raise ValueError("attn_varlen_bwd: dout must be bf16 [T, H]")
@@ -649,27 +685,42 @@ def attn_varlen_bwd(qkv, bqkv, seqs: PackedSeqs, out, lse, dout, dbqkv, heads, p
         raise ValueError("attn_varlen_bwd: dbqkv must be a contiguous fp32 [3H] vector")
     dqkv = torch.empty_like(qkv)
     work = _lib.workspace(heads * T_ * 4, qkv.device, "attn_rowdot")  # D = rowsum(dO∘O) [heads, T]
+    if gqa:
+        _lib.call("kfa_attn_gqa_bwd", _lib.ptr(qkv), _lib.ptr(bqkv), _lib.ptr(seqs.cu_dev), _lib.ptr(out),
+                  _lib.ptr(lse), _lib.ptr(dout), _lib.ptr(dqkv), _lib.ptr(dbqkv), seqs.B, T_, seqs.max_seqlen, heads,
+                  kv_heads, 128, int(bool(causal)), 1.0 / math.sqrt(128), float(p), hash_key(seed), _lib.ptr(work),
+                  _lib.stream())
+        return dqkv
     _lib.call("kfa_attn_causal_bwd" if causal else "kfa_attn_varlen_bwd", _lib.ptr(qkv), _lib.ptr(bqkv),
               _lib.ptr(seqs.cu_dev), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(dout), _lib.ptr(dqkv), _lib.ptr(dbqkv), seqs.B, T_, seqs.max_seqlen, heads, H // heads,
               1.0 / math.sqrt(H // heads), float(p), hash_key(seed), _lib.ptr(work), _lib.stream())
     return dqkv
 
 
-def attention_varlen_reference(qkv, bqkv, seqs: PackedSeqs, heads, keep=None, keep_scale=1.0, causal=False):
+def attention_varlen_reference(qkv, bqkv, seqs: PackedSeqs, heads, keep=None, keep_scale=1.0, causal=False,
+                               kv_heads=None):
     """Plain fp32 PyTorch: ctx [T, H] of the packed batch, one sequence at a time; the
     unowned rows are zero.  ``keep`` (optional): per sequence a [heads, len, len] 0/1
     dropout keep mask, kept probabilities scaled by ``keep_scale``.  ``causal``: scores
-    above each sequence's diagonal are -inf before the softmax."""
+    above each sequence's diagonal are -inf before the softmax.  ``kv_heads``: grouped-query
+    layout [T, (heads + 2·kv_heads)·d], query head h reads KV head ``h // (heads // kv_heads)``."""
     T_, W3 = qkv.shape
-    H = W3 // 3
-    d = H // heads
+    kvh = heads if kv_heads is None else kv_heads
+    if kvh < 1 or heads % kvh or W3 % (heads + 2 * kvh):
+        raise ValueError(f"attention_varlen_reference: qkv {tuple(qkv.shape)} is not (heads + 2·kv_heads)·d wide "
+                         f"with kv_heads dividing heads (heads={heads}, kv_heads={kvh})")
+    d = W3 // (heads + 2 * kvh)
+    H = heads * d
     x = qkv.float()
     if bqkv is not None:
         x = x + bqkv.float()
     cu = seqs.cu_host.tolist()
     parts = []
     for i in range(len(cu) - 1):
-        q, k, v = x[cu[i]:cu[i + 1]].view(-1, 3, heads, d).permute(1, 2, 0, 3)   # [heads, len, d]
+        xs = x[cu[i]:cu[i + 1]]
+        q = xs[:, :H].view(-1, heads, d).permute(1, 0, 2)                        # [heads, len, d]
+        k, v = (xs[:, H + j * kvh * d:H + (j + 1) * kvh * d].view(-1, kvh, d).permute(1, 0, 2)
+                .repeat_interleave(heads // kvh, 0) for j in (0, 1))
         sc = (q @ k.transpose(-1, -2)) / math.sqrt(d)
         if causal:
             sc = sc.masked_fill(~torch.tril(torch.ones_like(sc, dtype=torch.bool)), float("-inf"))
@@ -743,13 +794,18 @@ class EncoderLayerFn(torch.autograd.Function):
         # the backward) and of its output (taken from by the backward); cfg[9] (optional):
         # the PackedSeqs of a packed batch — x is then [rows, H], attention runs per
         # sequence through the varlen kernels (B and S are not used) and key_bias is None;
-        # cfg[10] (optional): causal attention (a decoder layer), packed batches only
+        # cfg[10] (optional): causal attention (a decoder layer), packed batches only;
+        # cfg[11] (optional): kv_heads of grouped-query attention (wqkv [(heads + 2·kv_heads)·d, H],
+        # d = H // heads = 128), packed batches only
         B, S, heads, ph, pa, seed, eps = cfg[:7]
         ctx.joins = (tuple(cfg[7:9]) + (None, None))[:2]
         seqs = cfg[9] if len(cfg) > 9 else None
         causal = bool(cfg[10]) if len(cfg) > 10 else False
+        kv_heads = cfg[11] if len(cfg) > 11 else None
         if causal and seqs is None:
             raise ValueError("EncoderLayerFn: causal attention needs a packed batch (cfg[9]: a PackedSeqs)")
+        if kv_heads is not None and seqs is None:
+            raise ValueError("EncoderLayerFn: grouped-query attention needs a packed batch (cfg[9]: a PackedSeqs)")
         _gemm.mark_weights_stale()  # the dgrad's cached weight transposes refresh at the next backward
         T, H = x.shape
         d = H // heads
@@ -771,7 +827,7 @@ class EncoderLayerFn(torch.autograd.Function):
         # attention
         qkv = mm(x, wqkv)                                                 # [T, 3H]
         if seqs is not None:
-            ctxr, lse = attn_varlen_fwd(qkv, bqkv, seqs, heads, pa, s_attn, causal=causal)
+            ctxr, lse = attn_varlen_fwd(qkv, bqkv, seqs, heads, pa, s_attn, causal=causal, kv_heads=kv_heads)
             att = (qkv, lse)
         elif fused:
             ctxr, lse, amask = attn_fwd(qkv, bqkv, key_bias, B, S, heads, pa, s_attn, want_mask=True) if ATTN_MASK \
@@ -810,6 +866,7 @@ class EncoderLayerFn(torch.autograd.Function):
         ctx.key_bias = key_bias
         ctx.seqs = seqs
         ctx.causal = causal
+        ctx.kv_heads = kv_heads
         return h2
 
     @staticmethod
@@ -851,7 +908,8 @@ class EncoderLayerFn(torch.autograd.Function):
         del dao
         if ctx.seqs is not None:
             qkv, lse = att
-            dqkv = attn_varlen_bwd(qkv, bqkv, ctx.seqs, ctxr, lse, dctxr, None, heads, pa, s_attn, causal=ctx.causal)
+            dqkv = attn_varlen_bwd(qkv, bqkv, ctx.seqs, ctxr, lse, dctxr, None, heads, pa, s_attn, causal=ctx.causal,
+                                   kv_heads=ctx.kv_heads)
             colsum_(dqkv, G(bqkv))  # as the fused path: one column-sum pass over the still-cached dqkv
             del dctxr
         elif fused:
@@ -901,12 +959,16 @@ class EncoderLayerFn(torch.autograd.Function):
 def encoder_layer_reference(x, key_bias, cfg, wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2):
     """Plain PyTorch fp32 reference (no dropout); cfg[9] (optional): the PackedSeqs of a
     packed batch (x [rows, H], attention per sequence, no key_bias); cfg[10] (optional):
-    causal attention, packed batches only."""
+    causal attention, packed batches only; cfg[11] (optional): kv_heads of grouped-query
+    attention, packed batches only."""
     B, S, heads, _, _, _, eps = cfg[:7]
     seqs = cfg[9] if len(cfg) > 9 else None
     causal = bool(cfg[10]) if len(cfg) > 10 else False
+    kv_heads = cfg[11] if len(cfg) > 11 else None
     if causal and seqs is None:
         raise ValueError("encoder_layer_reference: causal attention needs a packed batch (cfg[9])")
+    if kv_heads is not None and seqs is None:
+        raise ValueError("encoder_layer_reference: grouped-query attention needs a packed batch (cfg[9])")
     T, H = x.shape
     d = H // heads
     f = lambda t: t.float()  # noqa: E731
@@ -915,7 +977,7 @@ def encoder_layer_reference(x, key_bias, cfg, wqkv, bqkv, wo, bo, g1, be1, w1, b
     if seqs is not None:
         if key_bias is not None:
             raise ValueError("encoder_layer_reference: a packed batch takes no key_bias")
-        a = attention_varlen_reference(qkv, None, seqs, heads, causal=causal)
+        a = attention_varlen_reference(qkv, None, seqs, heads, causal=causal, kv_heads=kv_heads)
     else:
         q, k, v = qkv.view(B, S, 3, heads, d).permute(2, 0, 3, 1, 4)
         sc = (q @ k.transpose(-1, -2)) / math.sqrt(d)

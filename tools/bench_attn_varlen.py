@@ -31,7 +31,8 @@ def timed(fn, iters):
     return a.elapsed_time(b) / iters
 
 
-def alternate(sides, rounds, iters):
+def alternate_rounds(sides, rounds, iters):
+    """{side: [ms per call of each round]}: every round times every side once, in turn."""
     for fn in sides.values():  # warm-up: code objects, workspaces, the GEMM tuner's choices
         for _ in range(3):
             fn()
@@ -40,7 +41,56 @@ def alternate(sides, rounds, iters):
     for _ in range(rounds):
         for k, fn in sides.items():
             t[k].append(timed(fn, iters))
-    return {k: (min(v), statistics.median(v)) for k, v in t.items()}
+    return t
+
+
+def alternate(sides, rounds, iters):
+    return {k: (min(v), statistics.median(v)) for k, v in alternate_rounds(sides, rounds, iters).items()}
+
+
+def gqa(rounds, kv_heads):
+    """--head-dim 128 --kv-heads K: 16 query heads of 128 (H = 2048, dropout 0.1), grouped-query
+    attention with K KV heads against the multi-head d = 128 kernels at the same query heads (the
+    same Q columns; K / V head c of the GQA batch is head c·g of the MHA batch), bidirectional and
+    causal: 32 sequences of 1024 tokens, and lengths uniform in [128, 1024].  The ratio is taken
+    per round (both sides timed back to back) and its spread over the rounds is printed."""
+    d = torch.device("cuda")
+    g = torch.Generator().manual_seed(0)
+    torch.manual_seed(0)
+    h, hd, p, S = 16, 128, 0.1, 1024
+    H, grp = h * hd, h // kv_heads
+    for name, lens in (("32 x 1024", torch.full((32,), S)), ("32, uniform in [128, 1024]",
+                                                            torch.randint(128, S + 1, (32,), generator=g))):
+        rows = int(lens.sum())
+        seqs = T.PackedSeqs(torch.cat([torch.zeros(1, dtype=torch.long), lens.cumsum(0)]), rows, S, d)
+        mha = torch.randn(rows, 3, h, hd, device=d).to(torch.bfloat16)
+        qkv = {"mha": mha.view(rows, 3 * H),
+               "gqa": torch.cat([mha[:, 0].reshape(rows, H), mha[:, 1, ::grp].reshape(rows, -1),
+                                 mha[:, 2, ::grp].reshape(rows, -1)], 1).contiguous()}
+        kvh = {"mha": None, "gqa": kv_heads}
+        dout = torch.randn(rows, H, device=d).to(torch.bfloat16)
+
+        def fwd(k, c):
+            return T.attn_varlen_fwd(qkv[k], None, seqs, h, p, 7, causal=c, kv_heads=kvh[k])
+
+        def both(k, c):
+            out, lse = fwd(k, c)
+            T.attn_varlen_bwd(qkv[k], None, seqs, out, lse, dout, None, h, p, 7, causal=c, kv_heads=kvh[k])
+
+        sides = {}
+        for c in (False, True):
+            for k in ("mha", "gqa"):  # the default arguments bind this iteration's values
+                sides[("causal" if c else "bidir", k, "fwd")] = lambda k=k, c=c: fwd(k, c)
+                sides[("causal" if c else "bidir", k, "fwd+bwd")] = lambda k=k, c=c: both(k, c)
+        t = alternate_rounds(sides, rounds, 20)
+        print(f"attention, {name}: {rows} rows, {h} query heads of {hd}, {kv_heads} KV heads")
+        for (c, k, w), v in t.items():
+            print(f"  {c:6s} {k} {w:8s} min {min(v) * 1e3:7.1f} us  median {statistics.median(v) * 1e3:7.1f} us", flush=True)
+        for c in ("bidir", "causal"):
+            for w in ("fwd", "fwd+bwd"):
+                r = [a / b for a, b in zip(t[(c, "gqa", w)], t[(c, "mha", w)])]
+                print(f"  {c} {w}: gqa / mha = {statistics.median(r):.3f} (median of the per-round ratios; "
+                      f"min {min(r):.3f}, max {max(r):.3f})")
 
 
 def head_dims(rounds):
@@ -123,7 +173,14 @@ def main():
     ap.add_argument("--head-dim", type=int, default=64, choices=[64, 128],
                     help="128: d = 128 (6 heads) against d = 64 (12 heads) at H = 768; with --causal: the head dim of "
                          "that comparison")
+    ap.add_argument("--kv-heads", type=int, default=None,
+                    help="with --head-dim 128: grouped-query attention with this many KV heads against the multi-head "
+                         "kernels, both at 16 query heads")
     args = ap.parse_args()
+    if args.kv_heads is not None:
+        if args.head_dim != 128 or args.kv_heads < 1 or 16 % args.kv_heads:
+            ap.error("--kv-heads needs --head-dim 128 and a divisor of the 16 query heads")
+        return gqa(args.rounds, args.kv_heads)
     if args.causal:
         return causal(args.rounds, args.head_dim)
     if args.head_dim == 128:
