@@ -2217,10 +2217,10 @@ KFA_API int kfa_attn_bwd(const void* qkv, const float* bqkv, const float* key_bi
 // The grid comes from max_seqlen alone: no device-to-host sync.  d = 128 goes to the kernels of
 // attention_d128.hip (same contracts, same arguments).
 long kfa_attn_d128_blocks(int B, int max_seqlen, int heads);
-int kfa_attn_d128_fwd(bool causal, const void* qkv, const float* bqkv, const int* cu, void* out, float* lse, int B,
-                      int T, int max_seqlen, int heads, int kv_heads, float qscale, uint32_t th, float ds,
-                      uint64_t seed, hipStream_t st);
-int kfa_attn_d128_bwd(bool causal, const void* qkv, const float* bqkv, const int* cu, const void* out,
+int kfa_attn_d128_fwd(bool causal, int window, const void* qkv, const float* bqkv, const int* cu, void* out,
+                      float* lse, int B, int T, int max_seqlen, int heads, int kv_heads, float qscale, uint32_t th,
+                      float ds, uint64_t seed, hipStream_t st);
+int kfa_attn_d128_bwd(bool causal, int window, const void* qkv, const float* bqkv, const int* cu, const void* out,
                       const float* lse, const void* dout, void* dqkv, float* dbqkv, int B, int T, int max_seqlen,
                       int heads, int kv_heads, float qscale, uint32_t th, float ds, uint64_t seed, float* work,
                       hipStream_t st);
@@ -2236,7 +2236,7 @@ KFA_API int kfa_attn_varlen_fwd(const void* qkv, const float* bqkv, const int* c
   if (!qkv || !bqkv || !cu || !out || !lse || !attn_varlen_args_ok(B, T, max_seqlen, heads, d)) return -1;
   const uint32_t th = attn_drop_t16(p);
   if (d == 128)
-    return kfa_attn_d128_fwd(false, qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, heads, qscale, th, attn_drop_scale(th),
+    return kfa_attn_d128_fwd(false, 0, qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, heads, qscale, th, attn_drop_scale(th),
                              (uint64_t)seed, st);
   const dim3 grid((unsigned)((long)B * heads * ((max_seqlen + BLK - 1) / BLK)));
   hipLaunchKernelGGL(attn_varlen_fwd_kernel, grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv, cu, (bf16_t*)out, lse, B,
@@ -2255,7 +2255,7 @@ KFA_API int kfa_attn_varlen_bwd(const void* qkv, const float* bqkv, const int* c
   const uint32_t th = attn_drop_t16(p);
   const float ds = attn_drop_scale(th);
   if (d == 128)
-    return kfa_attn_d128_bwd(false, qkv, bqkv, cu, out, lse, dout, dqkv, dbqkv, B, T, max_seqlen, heads, heads, qscale, th, ds,
+    return kfa_attn_d128_bwd(false, 0, qkv, bqkv, cu, out, lse, dout, dqkv, dbqkv, B, T, max_seqlen, heads, heads, qscale, th, ds,
                              (uint64_t)seed, work, st);
   hipLaunchKernelGGL(attn_varlen_rowdot_kernel, dim3((unsigned)(((long)T * heads + 255) / 256)), dim3(256), 0, st,
                      (const bf16_t*)dout, (const bf16_t*)out, cu, work, B, T, heads);
@@ -2279,7 +2279,7 @@ KFA_API int kfa_attn_causal_fwd(const void* qkv, const float* bqkv, const int* c
   if (!qkv || !bqkv || !cu || !out || !lse || !attn_varlen_args_ok(B, T, max_seqlen, heads, d)) return -1;
   const uint32_t th = attn_drop_t16(p);
   if (d == 128)
-    return kfa_attn_d128_fwd(true, qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, heads, qscale, th, attn_drop_scale(th),
+    return kfa_attn_d128_fwd(true, 0, qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, heads, qscale, th, attn_drop_scale(th),
                              (uint64_t)seed, st);
   hipLaunchKernelGGL(attn_causal_fwd_kernel, dim3(attn_causal_grid(B, max_seqlen, heads)), dim3(256), 0, st,
                      (const bf16_t*)qkv, bqkv, cu, (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th,
@@ -2296,7 +2296,7 @@ KFA_API int kfa_attn_causal_bwd(const void* qkv, const float* bqkv, const int* c
   const uint32_t th = attn_drop_t16(p);
   const float ds = attn_drop_scale(th);
   if (d == 128)
-    return kfa_attn_d128_bwd(true, qkv, bqkv, cu, out, lse, dout, dqkv, dbqkv, B, T, max_seqlen, heads, heads, qscale, th, ds,
+    return kfa_attn_d128_bwd(true, 0, qkv, bqkv, cu, out, lse, dout, dqkv, dbqkv, B, T, max_seqlen, heads, heads, qscale, th, ds,
                              (uint64_t)seed, work, st);
   hipLaunchKernelGGL(attn_varlen_rowdot_kernel, dim3((unsigned)(((long)T * heads + 255) / 256)), dim3(256), 0, st,
                      (const bf16_t*)dout, (const bf16_t*)out, cu, work, B, T, heads);
@@ -2322,7 +2322,7 @@ KFA_API int kfa_attn_gqa_fwd(const void* qkv, const float* bqkv, const int* cu, 
                              unsigned long long seed, hipStream_t st) {
   if (!qkv || !bqkv || !cu || !out || !lse || !attn_gqa_args_ok(B, T, max_seqlen, heads, kv_heads, d)) return -1;
   const uint32_t th = attn_drop_t16(p);
-  return kfa_attn_d128_fwd(causal != 0, qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, kv_heads, qscale, th,
+  return kfa_attn_d128_fwd(causal != 0, 0, qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, kv_heads, qscale, th,
                            attn_drop_scale(th), (uint64_t)seed, st);
 }
 
@@ -2335,6 +2335,33 @@ KFA_API int kfa_attn_gqa_bwd(const void* qkv, const float* bqkv, const int* cu, 
     return -1;
   if (!work) return -3;
   const uint32_t th = attn_drop_t16(p);
-  return kfa_attn_d128_bwd(causal != 0, qkv, bqkv, cu, out, lse, dout, dqkv, dbqkv, B, T, max_seqlen, heads, kv_heads,
+  return kfa_attn_d128_bwd(causal != 0, 0, qkv, bqkv, cu, out, lse, dout, dqkv, dbqkv, B, T, max_seqlen, heads, kv_heads,
+                           qscale, th, attn_drop_scale(th), (uint64_t)seed, work, st);
+}
+
+// Sliding-window causal attention over a packed batch, head dim 128 only (attention_d128.hip, the
+// windowed instances): query i of a sequence sees its keys max(0, i - window + 1) .. i.  The arguments
+// are those of kfa_attn_gqa_* with `window` (>= 1) in place of `causal`; kv_heads == heads: multi-head
+// attention.  A window of max_seqlen or more runs the causal instances.
+KFA_API int kfa_attn_window_fwd(const void* qkv, const float* bqkv, const int* cu, void* out, float* lse, int B, int T,
+                                int max_seqlen, int heads, int kv_heads, int d, int window, float qscale, float p,
+                                unsigned long long seed, hipStream_t st) {
+  if (!qkv || !bqkv || !cu || !out || !lse || window < 1 || !attn_gqa_args_ok(B, T, max_seqlen, heads, kv_heads, d))
+    return -1;
+  const uint32_t th = attn_drop_t16(p);
+  return kfa_attn_d128_fwd(true, window, qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, kv_heads, qscale, th,
+                           attn_drop_scale(th), (uint64_t)seed, st);
+}
+
+KFA_API int kfa_attn_window_bwd(const void* qkv, const float* bqkv, const int* cu, const void* out, const float* lse,
+                                const void* dout, void* dqkv, float* dbqkv, int B, int T, int max_seqlen, int heads,
+                                int kv_heads, int d, int window, float qscale, float p, unsigned long long seed,
+                                float* work, hipStream_t st) {
+  if (!qkv || !bqkv || !cu || !out || !lse || !dout || !dqkv || window < 1 ||
+      !attn_gqa_args_ok(B, T, max_seqlen, heads, kv_heads, d))
+    return -1;
+  if (!work) return -3;
+  const uint32_t th = attn_drop_t16(p);
+  return kfa_attn_d128_bwd(true, window, qkv, bqkv, cu, out, lse, dout, dqkv, dbqkv, B, T, max_seqlen, heads, kv_heads,
                            qscale, th, attn_drop_scale(th), (uint64_t)seed, work, st);
 }

@@ -64,6 +64,19 @@
 //   query head would need g-way fp32 atomics into a scratch and a convert pass.)  The
 //   GQA = false instances compile to the instructions they had before the template
 //   argument existed; their trailing kv_heads argument is not read.
+// Sliding window (the WIN = true instances, causal only: query i sees keys max(0, i - window + 1) .. i;
+//   1 <= window < max_seqlen, a wider one runs the causal instances).  The window is a loop bound first:
+//   a 128-query block starts its key loop at block max(0, blk·128 - (window - 1)) / 64, a 64-key block
+//   ends its query loop (GQA: per query head) at the block of query `last key + window - 1`, so a
+//   workgroup streams at most (OB + window - 1) / 64 + 1 blocks whatever the length, and loads no image
+//   that none of its rows sees.  Per wave, tiles / slices / steps wholly below the band are skipped
+//   like those above the diagonal, and only tiles the lower edge crosses select on query - key >=
+//   window.  Forward: a wave's first blocks can lie wholly before a later row's window; such a row
+//   subtracts 0 instead of its (still kMasked) maximum, so P = 0 and alpha acts on zeros until its first
+//   visible key.  Grid: the bidirectional order (blocks of one (sequence, head) are neighbours: they
+//   stream overlapping bands, and the work per block is nearly uniform, so heaviest-first has no
+//   purpose), each (sequence, head) from its heavier end (queries: last block first; keys: first).
+//   The other instances compile to the instructions they had before; their trailing window is not read.
 #include "attn_tile.h"
 
 namespace {
@@ -181,11 +194,14 @@ __device__ __forceinline__ void store_tile_d(const char* st, bf16_t* __restrict_
 // the workgroup's owner block of OB rows; false: the block starts past its sequence.
 // Bidirectional: blocks of one (sequence, head) are neighbours in the grid (they stream the
 // same K / V).  Causal: block index major, heaviest first (HIGH_FIRST: the last query block
-// streams the most keys; for dK / dV the first key block streams the most queries).
+// streams the most keys; for dK / dV the first key block streams the most queries).  Window: the
+// bidirectional order (neighbouring blocks stream overlapping bands), within one (sequence, head)
+// from the end that can be heavier (HIGH_FIRST; the band is cut short at the sequence start for
+// queries, at its end for keys), so that the grid does not end on the heaviest blocks.
 struct OwnBlock {
   int blk, b, h, s0, len;
 };
-template <int OB, bool CAUSAL, bool HIGH_FIRST>
+template <int OB, bool CAUSAL, bool HIGH_FIRST, bool WIN = false>
 __device__ __forceinline__ bool own_block(const int* __restrict__ cu, int B, int T, int heads, int max_seqlen,
                                           OwnBlock& w) {
   const int nb = (max_seqlen + OB - 1) / OB;
@@ -197,6 +213,7 @@ __device__ __forceinline__ bool own_block(const int* __restrict__ cu, int B, int
   } else {
     sh = blockIdx.x / nb;
     w.blk = blockIdx.x - sh * nb;
+    if constexpr (WIN && HIGH_FIRST) w.blk = nb - 1 - w.blk;
   }
   w.b = sh / heads;
   w.h = sh - w.b * heads;
@@ -218,18 +235,19 @@ __device__ __forceinline__ int kv_head(int h, int heads, int kv_heads) {
 // forward: workgroup per (sequence, head, block of 64·RT queries); wave w owns queries 16·RT·w.. as
 // register operands, streams 64-key blocks (K, V images), online softmax per block, P feeds P·V
 // from registers
-template <int RT, bool CAUSAL, bool GQA>
+template <int RT, bool CAUSAL, bool GQA, bool WIN>
 __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_fwd_kernel(
     const bf16_t* __restrict__ qkv, const float* __restrict__ bqkv, const int* __restrict__ cu,
     bf16_t* __restrict__ out, float* __restrict__ lse, int B, int T, int heads, int max_seqlen, float qscale,
-    uint32_t thresh, float dscale, uint64_t seed, int kv_heads) {
+    uint32_t thresh, float dscale, uint64_t seed, int kv_heads, int window) {
+  static_assert(CAUSAL || !WIN, "a window is a band below the diagonal");
   constexpr int OB = 64 * RT, WR = 16 * RT;
   __shared__ __attribute__((aligned(16))) char sm[2 * IMG];  // K, V images (32 KiB)
   char* Ki = sm;
   char* Vi = sm + IMG;
   const int tid = threadIdx.x, lane0 = tid & 63, wave = tid >> 6, fr0 = lane0 & 15, fq0 = lane0 >> 4;
   OwnBlock w;
-  if (!own_block<OB, CAUSAL, true>(cu, B, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
+  if (!own_block<OB, CAUSAL && !WIN, true, WIN>(cu, B, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
   const int h = w.h, H = heads * HD;
   const int hk = kv_head<GQA>(h, heads, kv_heads), VC = GQA ? H + kv_heads * HD : 2 * H;  // KV head, V's first column
   const long W3 = GQA ? (long)H + 2L * kv_heads * HD : 3L * H, q0 = (long)w.s0 + (long)w.blk * OB;
@@ -257,11 +275,13 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_fwd_kernel(
 #pragma unroll
     for (int dt = 0; dt < 8; dt++) o[dt][qt] = floatx4{0.f, 0.f, 0.f, 0.f};
   }
-  // keys some query of the block sees: the loop bound is the causal mask below the diagonal
+  // keys some query of the block sees: the loop bound is the causal mask below the diagonal, and
+  // (window) the first block is the one that holds the first key of the block's first query
   const int nkb = ((CAUSAL ? w.blk * OB + qlive : w.len) + SB - 1) / SB;
-  for (int j = 0; j < nkb; j++) {
+  const int j0 = WIN ? max(0, w.blk * OB - (window - 1)) / SB : 0;
+  for (int j = j0; j < nkb; j++) {
     const int klive = min(SB, w.len - j * SB);  // >= 1
-    if (j > 0) __syncthreads();                 // every wave is done with key block j-1
+    if (j > j0) __syncthreads();                // every wave is done with key block j-1
     {
       const int col[2] = {H + hk * HD, VC + hk * HD};
       const bool tf[2] = {true, true};
@@ -274,19 +294,22 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_fwd_kernel(
     __syncthreads();
     // keys of this block the wave's queries can see: the live ones, causal: up to its last query
     const int kend = CAUSAL ? min(klive, qabs + WR - j * SB) : klive;
-    if (!wlive || kend <= 0) continue;
+    // window: keys of this block before kbeg are before the window of the wave's first query, so of all
+    const int kbeg = WIN ? qabs - (window - 1) - j * SB : 0;
+    if (!wlive || kend <= 0 || (WIN && kbeg >= kend)) continue;
     // the lane's indices are formed again in each block: hoisted out of the loop, the LDS addresses
     // derived from them would not fit the register budget
     int lane = lane0;
     asm volatile("" : "+v"(lane));
     const int fr = lane & 15, fq = lane >> 4;
-    // s[kt][qt][r] = score(q = qb + 16qt + fr, key = 16kt + 4fq + r); tiles past kend stay 0 until masked
+    // s[kt][qt][r] = score(q = qb + 16qt + fr, key = 16kt + 4fq + r); tiles past kend (window: or
+    // before kbeg) stay 0 until masked
     floatx4 s[4][RT];
 #pragma unroll
     for (int kt = 0; kt < 4; kt++) {
 #pragma unroll
       for (int qt = 0; qt < RT; qt++) s[kt][qt] = floatx4{0.f, 0.f, 0.f, 0.f};
-      if (kt * 16 < kend) {
+      if (kt * 16 < kend && (!WIN || kt * 16 + 15 >= kbeg)) {
 #pragma unroll
         for (int ks = 0; ks < 4; ks++) {
           const short8 a = rd_rowd(Ki, kt * 16 + fr, ks * 32 + fq * 8);
@@ -309,6 +332,22 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_fwd_kernel(
                 s[kt][qt][r] = above_diag(qabs + 16 * qt + fr, j * SB + kt * 16 + 4 * fq + r, kMasked, s[kt][qt][r]);
           }
       }
+      if constexpr (WIN) {
+        // tiles the lower window edge crosses or that lie before it (the wave's last query does not see
+        // the tile's first key): query - key >= window is masked
+        if (qabs + WR - 1 - j * SB >= window) {
+#pragma unroll
+          for (int kt = 0; kt < 4; kt++)
+            if (qabs + WR - 1 - (j * SB + kt * 16) >= window) {
+#pragma unroll
+              for (int qt = 0; qt < RT; qt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++)
+                  s[kt][qt][r] = above_diag(window - 1, qabs + 16 * qt + fr - (j * SB + kt * 16 + 4 * fq + r), kMasked,
+                                            s[kt][qt][r]);
+            }
+        }
+      }
     } else if (klive < SB) {
 #pragma unroll
       for (int kt = 0; kt < 4; kt++)
@@ -328,15 +367,19 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_fwd_kernel(
         for (int r = 0; r < 4; r++) mx = fmaxf(mx, s[kt][qt][r]);
       mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      // finite: key 0 of the sequence is live and visible to every query, and block 0 comes first
+      // finite: key 0 of the sequence is live and visible to every query, and block 0 comes first.
+      // Window: the wave's first blocks can lie wholly before a later row's window; while such a row has
+      // seen no key (mn == kMasked) 0 is subtracted instead, so P = exp2(kMasked) = 0 and alpha = 0 on
+      // l = 0, O = 0, until its first visible key makes mn finite (every query sees itself)
       const float mn = fmaxf(m[qt], mx);
-      const float alpha = __builtin_amdgcn_exp2f(m[qt] - mn);
+      const float sub = WIN && mn == kMasked ? 0.f : mn;
+      const float alpha = __builtin_amdgcn_exp2f(m[qt] - sub);
       float sum = 0.f;
 #pragma unroll
       for (int kt = 0; kt < 4; kt++)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-          const float e = __builtin_amdgcn_exp2f(s[kt][qt][r] - mn);
+          const float e = __builtin_amdgcn_exp2f(s[kt][qt][r] - sub);
           s[kt][qt][r] = e;
           sum += e;
         }
@@ -352,7 +395,7 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_fwd_kernel(
         const uint64_t row = (uint64_t)h * T + (uint64_t)(q0 + qb + qt * 16 + fr);
 #pragma unroll
         for (int kp = 0; kp < 2; kp++)
-          if (kp * 32 < kend) {  // a slice past kend holds P = 0 only
+          if (kp * 32 < kend && (!WIN || kp * 32 + 31 >= kbeg)) {  // a slice past kend (before kbeg) holds P = 0 only
 #pragma unroll
             for (int r = 0; r < 4; r++) {
               const uint32_t hh = attn_pair_hash(seed, row, max_seqlen, j * SB + 32 * kp + 4 * fq + r);
@@ -366,7 +409,7 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_fwd_kernel(
     // 32ks + 16 + 4fq + r}, V's rows are read in the same order
 #pragma unroll
     for (int ks = 0; ks < 2; ks++)
-      if (ks * 32 < kend) {
+      if (ks * 32 < kend && (!WIN || ks * 32 + 31 >= kbeg)) {
         short8 b[RT];
 #pragma unroll
         for (int qt = 0; qt < RT; qt++) b[qt] = pack_pair(s[2 * ks][qt], s[2 * ks + 1][qt]);
@@ -423,12 +466,13 @@ __global__ KFA_NO_PK_F32 void attn_d128_rowdot_kernel(const bf16_t* __restrict__
 // (K and V rows as register operands) and streams 64-query blocks (Q, dO images); causal: from the
 // query block that holds its first key on.  GQA: the owner is a KV head and the Q / dO blocks of
 // its g query heads stream past the same K / V registers and accumulators
-template <int RT, bool CAUSAL, bool GQA>
+template <int RT, bool CAUSAL, bool GQA, bool WIN>
 __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_kv_kernel(
     const bf16_t* __restrict__ qkv, const float* __restrict__ bqkv, const int* __restrict__ cu,
     const float* __restrict__ lse, const float* __restrict__ Dq, const bf16_t* __restrict__ dout,
     bf16_t* __restrict__ dqkv, float* __restrict__ dbqkv, int B, int T, int heads, int max_seqlen, float qscale,
-    uint32_t thresh, float dscale, uint64_t seed, int kv_heads) {
+    uint32_t thresh, float dscale, uint64_t seed, int kv_heads, int window) {
+  static_assert(CAUSAL || !WIN, "a window is a band below the diagonal");
   constexpr int OB = 64 * RT, WR = 16 * RT;
   __shared__ __attribute__((aligned(16))) char sm[2 * IMG];  // Q, dO images (32 KiB)
   char* Qi = sm;
@@ -436,7 +480,7 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_kv_kernel(
   const int tid = threadIdx.x, lane0 = tid & 63, wave = tid >> 6, fr0 = lane0 & 15, fq0 = lane0 >> 4;
   OwnBlock w;
   // GQA: the owner is a KV head; w.h counts KV heads and the query heads w.h·g .. w.h·g + g-1 stream past it
-  if (!own_block<OB, CAUSAL, false>(cu, B, T, GQA ? kv_heads : heads, max_seqlen, w)) return;  // uniform, before any barrier
+  if (!own_block<OB, CAUSAL && !WIN, false, WIN>(cu, B, T, GQA ? kv_heads : heads, max_seqlen, w)) return;  // uniform, before any barrier
   const int hk = w.h, H = heads * HD, g = GQA ? heads / kv_heads : 1, VC = GQA ? H + kv_heads * HD : 2 * H;
   const long W3 = GQA ? (long)H + 2L * kv_heads * HD : 3L * H, k0 = (long)w.s0 + (long)w.blk * OB;
   if (w.blk == 0 && w.b == B - 1) {
@@ -467,10 +511,12 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_kv_kernel(
 #pragma unroll
     for (int kt = 0; kt < RT; kt++) dvT[dt][kt] = dkT[dt][kt] = floatx4{0.f, 0.f, 0.f, 0.f};
   const int i0 = CAUSAL ? (w.blk * OB) / SB : 0;  // the loop bound is the causal mask above the diagonal
+  // window: the last streamed block holds the last query that sees the block's last key (or the sequence end)
+  const int nqe = WIN ? min(w.len - 1, w.blk * OB + klive - 1 + window - 1) / SB + 1 : nqb;
   // one flattened loop over (query head of the group, query block): the accumulators, the barriers
   // and the image loads do not know where one query head ends and the next begins
-  const int nq = nqb - i0;       // query blocks streamed per query head
-  int h = hk * g, wrap = nqb;    // the streamed block's query head; the counter at which the next one begins
+  const int nq = nqe - i0;       // query blocks streamed per query head
+  int h = hk * g, wrap = nqe;    // the streamed block's query head; the counter at which the next one begins
   for (int u = i0; u < i0 + nq * g; u++) {
     int i = u;  // the streamed query block
     if constexpr (GQA) {
@@ -478,7 +524,7 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_kv_kernel(
         wrap += nq;
         h++;
       }
-      i = u - (wrap - nqb);
+      i = u - (wrap - nqe);
     }
     const int qlive = min(SB, w.len - i * SB);
     const long qrow0 = (long)w.s0 + (long)i * SB;
@@ -508,7 +554,9 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_kv_kernel(
       if (32 * j >= qlive) break;
       const int qa = i * SB + 32 * j;  // the step's first query in the sequence
       if (CAUSAL && qa + 31 < kabs) continue;
+      if (WIN && qa - (kabs + WR - 1) >= window) break;  // no query of this or a later step sees a key of the wave
       const bool diag = CAUSAL && qa < kabs + WR - 1;  // some pair of the step has key > query
+      const bool low = WIN && qa + 31 - kabs >= window;  // some pair of the step has query - key >= window
       // s / dp[qt][kt][r]: (q = 32j + 16qt + 4fq + r, key = kw + 16kt + fr)
       floatx4 s[2][RT], dp[2][RT];
 #pragma unroll
@@ -545,6 +593,7 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_kv_kernel(
             // a pair with no query or no key (or, causal, above the diagonal) has P = 0, whatever lse holds
             bool ok = qok && keyok[kt];
             if (diag) ok = ok && kabs + 16 * kt + fr <= i * SB + qb4 + r;
+            if (low) ok = ok && i * SB + qb4 + r - (kabs + 16 * kt + fr) < window;
             const float p = ok ? __builtin_amdgcn_exp2f(fmaf(s[qt][kt][r], kLog2e, -lq)) : 0.f;
             float g = dp[qt][kt][r], pv = p;
             if (thresh) {
@@ -589,19 +638,20 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_kv_kernel(
 // query-owner dQ = dS·K: workgroup per (sequence, head, block of 64·RT queries); wave w owns queries
 // 16·RT·w.. (Q and dO rows as register operands) and streams 64-key blocks (K, V images), one 32-key
 // slice (a dropout hash pair and one dQ k-step) at a time
-template <int RT, bool CAUSAL, bool GQA>
+template <int RT, bool CAUSAL, bool GQA, bool WIN>
 __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_q_kernel(
     const bf16_t* __restrict__ qkv, const float* __restrict__ bqkv, const int* __restrict__ cu,
     const float* __restrict__ lse, const float* __restrict__ Dq, const bf16_t* __restrict__ dout,
     bf16_t* __restrict__ dqkv, float* __restrict__ dbqkv, int B, int T, int heads, int max_seqlen, float qscale,
-    uint32_t thresh, float dscale, uint64_t seed, int kv_heads) {
+    uint32_t thresh, float dscale, uint64_t seed, int kv_heads, int window) {
+  static_assert(CAUSAL || !WIN, "a window is a band below the diagonal");
   constexpr int OB = 64 * RT, WR = 16 * RT;
   __shared__ __attribute__((aligned(16))) char sm[2 * IMG];  // K, V images (32 KiB)
   char* Ki = sm;
   char* Vi = sm + IMG;
   const int tid = threadIdx.x, lane0 = tid & 63, wave = tid >> 6, fr0 = lane0 & 15, fq0 = lane0 >> 4;
   OwnBlock w;
-  if (!own_block<OB, CAUSAL, true>(cu, B, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
+  if (!own_block<OB, CAUSAL && !WIN, true, WIN>(cu, B, T, heads, max_seqlen, w)) return;  // uniform, before any barrier
   const int h = w.h, H = heads * HD;
   const int hk = kv_head<GQA>(h, heads, kv_heads), VC = GQA ? H + kv_heads * HD : 2 * H;  // KV head, V's first column
   const long W3 = GQA ? (long)H + 2L * kv_heads * HD : 3L * H, q0 = (long)w.s0 + (long)w.blk * OB;
@@ -636,9 +686,10 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_q_kernel(
 #pragma unroll
     for (int qt = 0; qt < RT; qt++) dqT[dt][qt] = floatx4{0.f, 0.f, 0.f, 0.f};
   const int nkb = ((CAUSAL ? w.blk * OB + qlive : w.len) + SB - 1) / SB;
-  for (int j = 0; j < nkb; j++) {
+  const int j0 = WIN ? max(0, w.blk * OB - (window - 1)) / SB : 0;  // as in the forward
+  for (int j = j0; j < nkb; j++) {
     const int klive = min(SB, w.len - j * SB);
-    if (j > 0) __syncthreads();  // every wave is done with key block j-1
+    if (j > j0) __syncthreads();  // every wave is done with key block j-1
     {
       const int col[2] = {H + hk * HD, VC + hk * HD};
       const bool tf[2] = {true, true};
@@ -650,7 +701,8 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_q_kernel(
     }
     __syncthreads();
     const int kend = CAUSAL ? min(klive, qabs + WR - j * SB) : klive;
-    if (!wlive || kend <= 0) continue;
+    const int kbeg = WIN ? qabs - (window - 1) - j * SB : 0;  // as in the forward
+    if (!wlive || kend <= 0 || (WIN && kbeg >= kend)) continue;
     int lane = lane0;  // as in the forward
     asm volatile("" : "+v"(lane));
     const int fr = lane & 15, fq = lane >> 4;
@@ -658,13 +710,15 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_q_kernel(
 #pragma unroll
     for (int c = 0; c < 2; c++) {
       if (c * 32 >= kend) break;
+      if (WIN && c * 32 + 31 < kbeg) continue;
       const bool diag = CAUSAL && j * SB + c * 32 + 31 > qabs;  // some pair of the slice has key > query
+      const bool low = WIN && qabs + WR - 1 - (j * SB + c * 32) >= window;  // some pair has query - key >= window
       floatx4 s[2][RT], dp[2][RT];
 #pragma unroll
       for (int u = 0; u < 2; u++) {
 #pragma unroll
         for (int qt = 0; qt < RT; qt++) s[u][qt] = dp[u][qt] = floatx4{0.f, 0.f, 0.f, 0.f};
-        if (c * 32 + u * 16 < kend) {
+        if (c * 32 + u * 16 < kend && (!WIN || c * 32 + u * 16 + 15 >= kbeg)) {
 #pragma unroll
           for (int ks = 0; ks < 4; ks++) {
             const short8 ak = rd_rowd(Ki, c * 32 + u * 16 + fr, ks * 32 + fq * 8);
@@ -688,6 +742,7 @@ __global__ __launch_bounds__(256, 2) KFA_NO_PK_F32 void attn_d128_bwd_q_kernel(
           for (int u = 0; u < 2; u++) {
             bool ok = qok[qt] && key + 16 * u < klive;  // else P = 0, whatever lse holds
             if (diag) ok = ok && j * SB + key + 16 * u <= qabs + 16 * qt + fr;
+            if (low) ok = ok && qabs + 16 * qt + fr - (j * SB + key + 16 * u) < window;
             const float p = ok ? __builtin_amdgcn_exp2f(fmaf(s[u][qt][r], kLog2e, -lq[qt])) : 0.f;
             float g = dp[u][qt][r];
             if (thresh) g = (u ? keep_hi(hh, thresh) : keep_lo(hh, thresh)) ? g * dscale : 0.f;
@@ -723,11 +778,11 @@ void launch_fwd(const void* qkv, const float* bqkv, const int* cu, void* out, fl
                 int heads, int kv_heads, float qscale, uint32_t th, float ds, uint64_t seed, hipStream_t st) {
   const dim3 grid((unsigned)((long)B * heads * ((max_seqlen + 64 * FWD_RT - 1) / (64 * FWD_RT))));
   if (kv_heads == heads)
-    hipLaunchKernelGGL((attn_d128_fwd_kernel<FWD_RT, CAUSAL, false>), grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
-                       cu, (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th, ds, seed, kv_heads);
+    hipLaunchKernelGGL((attn_d128_fwd_kernel<FWD_RT, CAUSAL, false, false>), grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
+                       cu, (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th, ds, seed, kv_heads, 0);
   else
-    hipLaunchKernelGGL((attn_d128_fwd_kernel<FWD_RT, CAUSAL, true>), grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
-                       cu, (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th, ds, seed, kv_heads);
+    hipLaunchKernelGGL((attn_d128_fwd_kernel<FWD_RT, CAUSAL, true, false>), grid, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
+                       cu, (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th, ds, seed, kv_heads, 0);
 }
 
 // dK / dV then dQ.  GQA: the dK / dV grid is over KV heads, a workgroup does its group's g query heads
@@ -738,19 +793,54 @@ void launch_bwd(const void* qkv, const float* bqkv, const int* cu, const float* 
   const dim3 gkv((unsigned)((long)B * kv_heads * ((max_seqlen + 64 * KV_RT - 1) / (64 * KV_RT))));
   const dim3 gq((unsigned)((long)B * heads * ((max_seqlen + 64 * DQ_RT - 1) / (64 * DQ_RT))));
   if (kv_heads == heads) {
-    hipLaunchKernelGGL((attn_d128_bwd_kv_kernel<KV_RT, CAUSAL, false>), gkv, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
+    hipLaunchKernelGGL((attn_d128_bwd_kv_kernel<KV_RT, CAUSAL, false, false>), gkv, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
                        cu, lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th,
-                       ds, seed, kv_heads);
-    hipLaunchKernelGGL((attn_d128_bwd_q_kernel<DQ_RT, CAUSAL, false>), gq, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
+                       ds, seed, kv_heads, 0);
+    hipLaunchKernelGGL((attn_d128_bwd_q_kernel<DQ_RT, CAUSAL, false, false>), gq, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
                        cu, lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th,
-                       ds, seed, kv_heads);
+                       ds, seed, kv_heads, 0);
   } else {
-    hipLaunchKernelGGL((attn_d128_bwd_kv_kernel<KV_RT, CAUSAL, true>), gkv, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
+    hipLaunchKernelGGL((attn_d128_bwd_kv_kernel<KV_RT, CAUSAL, true, false>), gkv, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
                        cu, lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th,
-                       ds, seed, kv_heads);
-    hipLaunchKernelGGL((attn_d128_bwd_q_kernel<DQ_RT, CAUSAL, true>), gq, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
+                       ds, seed, kv_heads, 0);
+    hipLaunchKernelGGL((attn_d128_bwd_q_kernel<DQ_RT, CAUSAL, true, false>), gq, dim3(256), 0, st, (const bf16_t*)qkv, bqkv,
                        cu, lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale, th,
-                       ds, seed, kv_heads);
+                       ds, seed, kv_heads, 0);
+  }
+}
+
+// The windowed instances (causal, 1 <= window < max_seqlen): the same grids in the bidirectional order
+void launch_fwd_window(const void* qkv, const float* bqkv, const int* cu, void* out, float* lse, int B, int T,
+                       int max_seqlen, int heads, int kv_heads, int window, float qscale, uint32_t th, float ds,
+                       uint64_t seed, hipStream_t st) {
+  const dim3 grid((unsigned)((long)B * heads * ((max_seqlen + 64 * FWD_RT - 1) / (64 * FWD_RT))));
+  if (kv_heads == heads)
+    hipLaunchKernelGGL((attn_d128_fwd_kernel<FWD_RT, true, false, true>), grid, dim3(256), 0, st, (const bf16_t*)qkv,
+                       bqkv, cu, (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th, ds, seed, kv_heads, window);
+  else
+    hipLaunchKernelGGL((attn_d128_fwd_kernel<FWD_RT, true, true, true>), grid, dim3(256), 0, st, (const bf16_t*)qkv,
+                       bqkv, cu, (bf16_t*)out, lse, B, T, heads, max_seqlen, qscale, th, ds, seed, kv_heads, window);
+}
+
+void launch_bwd_window(const void* qkv, const float* bqkv, const int* cu, const float* lse, const float* work,
+                       const void* dout, void* dqkv, float* dbqkv, int B, int T, int max_seqlen, int heads,
+                       int kv_heads, int window, float qscale, uint32_t th, float ds, uint64_t seed, hipStream_t st) {
+  const dim3 gkv((unsigned)((long)B * kv_heads * ((max_seqlen + 64 * KV_RT - 1) / (64 * KV_RT))));
+  const dim3 gq((unsigned)((long)B * heads * ((max_seqlen + 64 * DQ_RT - 1) / (64 * DQ_RT))));
+  if (kv_heads == heads) {
+    hipLaunchKernelGGL((attn_d128_bwd_kv_kernel<KV_RT, true, false, true>), gkv, dim3(256), 0, st, (const bf16_t*)qkv,
+                       bqkv, cu, lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale,
+                       th, ds, seed, kv_heads, window);
+    hipLaunchKernelGGL((attn_d128_bwd_q_kernel<DQ_RT, true, false, true>), gq, dim3(256), 0, st, (const bf16_t*)qkv,
+                       bqkv, cu, lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale,
+                       th, ds, seed, kv_heads, window);
+  } else {
+    hipLaunchKernelGGL((attn_d128_bwd_kv_kernel<KV_RT, true, true, true>), gkv, dim3(256), 0, st, (const bf16_t*)qkv,
+                       bqkv, cu, lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale,
+                       th, ds, seed, kv_heads, window);
+    hipLaunchKernelGGL((attn_d128_bwd_q_kernel<DQ_RT, true, true, true>), gq, dim3(256), 0, st, (const bf16_t*)qkv,
+                       bqkv, cu, lse, work, (const bf16_t*)dout, (bf16_t*)dqkv, dbqkv, B, T, heads, max_seqlen, qscale,
+                       th, ds, seed, kv_heads, window);
   }
 }
 
@@ -762,26 +852,34 @@ long kfa_attn_d128_blocks(int B, int max_seqlen, int heads) {
   return (long)B * heads * ((max_seqlen + 64 * KV_RT - 1) / (64 * KV_RT));
 }
 
-// The d = 128 side of kfa_attn_varlen_fwd / kfa_attn_causal_fwd / kfa_attn_gqa_fwd: arguments already
-// checked there; kv_heads == heads: the multi-head kernels
-int kfa_attn_d128_fwd(bool causal, const void* qkv, const float* bqkv, const int* cu, void* out, float* lse, int B,
-                      int T, int max_seqlen, int heads, int kv_heads, float qscale, uint32_t th, float ds,
-                      uint64_t seed, hipStream_t st) {
-  if (causal)
+// The d = 128 side of kfa_attn_varlen_fwd / kfa_attn_causal_fwd / kfa_attn_gqa_fwd / kfa_attn_window_fwd:
+// arguments already checked there; kv_heads == heads: the multi-head kernels; window: 0 for none, else
+// >= 1 with causal.  A window that covers every sequence (>= max_seqlen) masks nothing below the
+// diagonal: it runs the causal instances.
+int kfa_attn_d128_fwd(bool causal, int window, const void* qkv, const float* bqkv, const int* cu, void* out,
+                      float* lse, int B, int T, int max_seqlen, int heads, int kv_heads, float qscale, uint32_t th,
+                      float ds, uint64_t seed, hipStream_t st) {
+  if (causal && window > 0 && window < max_seqlen)
+    launch_fwd_window(qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, kv_heads, window, qscale, th, ds, seed, st);
+  else if (causal)
     launch_fwd<true>(qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, kv_heads, qscale, th, ds, seed, st);
   else
     launch_fwd<false>(qkv, bqkv, cu, out, lse, B, T, max_seqlen, heads, kv_heads, qscale, th, ds, seed, st);
   return kfa_status();
 }
 
-// The d = 128 side of kfa_attn_varlen_bwd / kfa_attn_causal_bwd / kfa_attn_gqa_bwd; work: heads·T floats
-int kfa_attn_d128_bwd(bool causal, const void* qkv, const float* bqkv, const int* cu, const void* out,
+// The d = 128 side of kfa_attn_varlen_bwd / kfa_attn_causal_bwd / kfa_attn_gqa_bwd / kfa_attn_window_bwd;
+// work: heads·T floats; window as the forward's
+int kfa_attn_d128_bwd(bool causal, int window, const void* qkv, const float* bqkv, const int* cu, const void* out,
                       const float* lse, const void* dout, void* dqkv, float* dbqkv, int B, int T, int max_seqlen,
                       int heads, int kv_heads, float qscale, uint32_t th, float ds, uint64_t seed, float* work,
                       hipStream_t st) {
   hipLaunchKernelGGL(attn_d128_rowdot_kernel, dim3((unsigned)(((long)T * heads + 255) / 256)), dim3(256), 0, st,
                      (const bf16_t*)dout, (const bf16_t*)out, cu, work, B, T, heads);
-  if (causal)
+  if (causal && window > 0 && window < max_seqlen)
+    launch_bwd_window(qkv, bqkv, cu, lse, work, dout, dqkv, dbqkv, B, T, max_seqlen, heads, kv_heads, window, qscale,
+                      th, ds, seed, st);
+  else if (causal)
     launch_bwd<true>(qkv, bqkv, cu, lse, work, dout, dqkv, dbqkv, B, T, max_seqlen, heads, kv_heads, qscale, th, ds,
                      seed, st);
   else

@@ -46,6 +46,7 @@ class GptConfig:
     ln_eps: float = 1e-5
     init_range: float = 0.02
     kv_heads: Optional[int] = None  # grouped-query attention: K / V heads (divides heads; head dim 128 only)
+    window: Optional[int] = None    # sliding-window attention: a token sees its last `window` tokens (head dim 128 only)
 
     @classmethod
     def small(cls) -> "GptConfig":
@@ -63,6 +64,12 @@ class GptConfig:
         """The ``xl`` shape with grouped-query attention: 16 query heads share 4 K / V heads of 128
         (the QKV projection is [3072, 2048] instead of [6144, 2048])."""
         return cls(hidden=2048, layers=24, heads=16, kv_heads=4, intermediate=8192, max_position=2048)
+
+    @classmethod
+    def xl_swa(cls) -> "GptConfig":
+        """The ``xl_gqa`` shape for long documents: 8192 positions, each token attending to its
+        last 1024 (sliding-window attention: attention cost is linear in the length)."""
+        return cls(hidden=2048, layers=24, heads=16, kv_heads=4, intermediate=8192, max_position=8192, window=1024)
 
     @classmethod
     def tiny(cls) -> "GptConfig":
@@ -94,6 +101,12 @@ class GptLM(nn.Module):
                 raise ValueError(f"GptLM: kv_heads must divide heads (heads={cfg.heads}, kv_heads={cfg.kv_heads})")
             if H != cfg.heads * 128:
                 raise ValueError(f"GptLM: grouped-query attention needs head dim 128, got {H / cfg.heads:g} "
+                                 f"(hidden={H}, heads={cfg.heads})")
+        if cfg.window is not None:
+            if cfg.window < 1:
+                raise ValueError(f"GptLM: window must be >= 1, got {cfg.window}")
+            if H != cfg.heads * 128:
+                raise ValueError(f"GptLM: sliding-window attention needs head dim 128, got {H / cfg.heads:g} "
                                  f"(hidden={H}, heads={cfg.heads})")
         self.word_emb = nn.Parameter(torch.empty(V, H))
         self.pos_emb = nn.Parameter(torch.empty(cfg.max_position, H))
@@ -135,7 +148,7 @@ class GptLM(nn.Module):
         for i, layer in enumerate(self.layers):
             join_out = T.ResidualJoin() if (self.training and i + 1 < len(self.layers)) else None
             lcfg = (seqs.B, seqs.max_seqlen, cfg.heads, ph, pa, T.s64(T.mix_seed(step_seed, i)), cfg.ln_eps, join_in,
-                    join_out, seqs, True, cfg.kv_heads)
+                    join_out, seqs, True, cfg.kv_heads, cfg.window)
             h = T.EncoderLayerFn.apply(h, None, lcfg, *layer.params())
             join_in = join_out
         # decoder_xent means over all rows (ignored rows add 0): rescale to the rows with a
@@ -150,7 +163,8 @@ class GptLM(nn.Module):
         cfg = self.cfg
         f = lambda t: t.float()  # noqa: E731
         h = f(self.word_emb)[input_ids.reshape(-1)] + f(self.pos_emb)[position_ids.reshape(-1)]
-        lcfg = (seqs.B, seqs.max_seqlen, cfg.heads, 0.0, 0.0, 0, cfg.ln_eps, None, None, seqs, True, cfg.kv_heads)
+        lcfg = (seqs.B, seqs.max_seqlen, cfg.heads, 0.0, 0.0, 0, cfg.ln_eps, None, None, seqs, True, cfg.kv_heads,
+                cfg.window)
         for layer in self.layers:
             h = T.encoder_layer_reference(h, None, lcfg, *layer.params())
         logits = h @ f(self.word_emb).t() + f(self.dec_b)
@@ -187,11 +201,15 @@ def synthetic_lm_batch(cfg: GptConfig, rows: int, seq_len: int, min_len: int, ge
 
 def flops_per_step(cfg: GptConfig, lens) -> float:
     """Model FLOPs (fwd+bwd = 3x fwd) of one step on sequences of ``lens`` tokens; attention
-    counts the visible half of each score matrix; with ``kv_heads`` the QKV projection is
+    counts the visible half of each score matrix (with ``window`` the visible band,
+    ``Σ_i min(i + 1, window)`` pairs per sequence); with ``kv_heads`` the QKV projection is
     ``(heads + 2·kv_heads)·d`` wide."""
     Tk = float(sum(lens))
     H, I, L = cfg.hidden, cfg.intermediate, cfg.layers
-    attn = sum(2 * 2 * (n * (n + 1) / 2) * H for n in lens)
+    W = cfg.window
+    # pairs of a sequence of n tokens: rows 0..m-1 see i + 1 keys, the other n - m rows see W, m = min(n, W)
+    pairs = [n * (n + 1) / 2 if W is None else min(n, W) * (min(n, W) + 1) / 2 + (n - min(n, W)) * W for n in lens]
+    attn = sum(2 * 2 * pr * H for pr in pairs)
     Wqkv = 3 * H if cfg.kv_heads is None else H + 2 * cfg.kv_heads * (H // cfg.heads)
     per_layer = 2 * Tk * (Wqkv * H + H * H + 2 * H * I) + attn
     return 3.0 * (L * per_layer + 2 * Tk * H * cfg.padded_vocab)

@@ -66,6 +66,8 @@ _lib.register("kfa_attn_causal_fwd", [P, P, P, P, P, I, I, I, I, I, Fl, Fl, U64,
 _lib.register("kfa_attn_causal_bwd", [P, P, P, P, P, P, P, P, I, I, I, I, I, Fl, Fl, U64, P, P])
 _lib.register("kfa_attn_gqa_fwd", [P, P, P, P, P, I, I, I, I, I, I, I, Fl, Fl, U64, P])
 _lib.register("kfa_attn_gqa_bwd", [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, Fl, Fl, U64, P, P])
+_lib.register("kfa_attn_window_fwd", [P, P, P, P, P, I, I, I, I, I, I, I, Fl, Fl, U64, P])
+_lib.register("kfa_attn_window_bwd", [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, Fl, Fl, U64, P, P])
 
 # env KFA_FUSED_ATTN=0 falls back to the split kernels + batched library GEMMs
 FUSED_ATTN = os.environ.get("KFA_FUSED_ATTN", "1") != "0"
@@ -599,7 +601,7 @@ def _gqa(heads, kv_heads):
     return None if kv_heads is None or kv_heads == heads else kv_heads
 
 
-def _varlen_check(name, qkv, bqkv, seqs, heads, kv_heads=None):
+def _varlen_check(name, qkv, bqkv, seqs, heads, kv_heads=None, causal=False, window=None):
     if not isinstance(seqs, PackedSeqs):
         raise ValueError(f"{name}: seqs must be a PackedSeqs")
     if qkv.dim() != 2 or qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
@@ -622,6 +624,15 @@ def _varlen_check(name, qkv, bqkv, seqs, heads, kv_heads=None):
             raise ValueError(f"{name}: bqkv must be a contiguous fp32 [(heads + 2·kv_heads)·128] vector")
     elif heads <= 0 or W3 % (3 * heads) or W3 // (3 * heads) not in (64, 128):
         raise ValueError(f"{name}: head dim must be 64 or 128 (qkv {tuple(qkv.shape)}, heads={heads})")
+    if window is not None:
+        # sliding window: causal, >= 1, head dim 128 only (the d = 64 paired-block kernel has no banded form)
+        if not causal:
+            raise ValueError(f"{name}: a sliding window needs causal=True (window={window})")
+        if window < 1:
+            raise ValueError(f"{name}: window must be >= 1, got {window}")
+        if _gqa(heads, kv_heads) is None and W3 // (3 * heads) != 128:
+            raise ValueError(f"{name}: sliding-window attention needs head dim 128 (qkv {tuple(qkv.shape)}, "
+                             f"heads={heads}: head dim {W3 // (3 * heads)})")
     seqs.validate(T_)
     if not qkv.is_cuda or seqs.cu_dev.device != qkv.device:
         raise ValueError(f"{name}: qkv and the sequence table must be on the same GPU "
@@ -633,7 +644,7 @@ def _varlen_check(name, qkv, bqkv, seqs, heads, kv_heads=None):
     return bqkv
 
 
-def attn_varlen_fwd(qkv, bqkv, seqs: PackedSeqs, heads, p=0.0, seed=0, causal=False, kv_heads=None):
+def attn_varlen_fwd(qkv, bqkv, seqs: PackedSeqs, heads, p=0.0, seed=0, causal=False, kv_heads=None, window=None):
     """(ctx [T, H], lse [heads, T]) of per-sequence softmax((q+b)(k+b)ᵀ/√d)·(v+b) over the
     packed batch ``seqs`` (``csrc/kernels/attention.hip``: attn_varlen_fwd_kernel; head dim
     128: ``attention_d128.hip``, same contracts); the unowned rows of ctx are zero.  Dropout: hash row ``h·T + token row``, key index
@@ -641,9 +652,20 @@ def attn_varlen_fwd(qkv, bqkv, seqs: PackedSeqs, heads, p=0.0, seed=0, causal=Fa
     keys 0..i of its sequence (attn_causal_fwd_kernel: the masked half is not computed).
     ``kv_heads`` (other than None / ``heads``): grouped-query attention, head dim 128 only:
     qkv [T, (heads + 2·kv_heads)·128] = Q heads | K heads | V heads, query head h reads KV
-    head ``h // (heads // kv_heads)``; ctx [T, heads·128]; the hash row is the query head's."""
-    bqkv = _varlen_check("attn_varlen_fwd", qkv, bqkv, seqs, heads, kv_heads)
+    head ``h // (heads // kv_heads)``; ctx [T, heads·128]; the hash row is the query head's.
+    ``window`` (with ``causal``, head dim 128 only, multi-head or grouped-query): query i sees
+    keys max(0, i - window + 1)..i of its sequence, ``window`` keys with itself (the windowed
+    instances of ``attention_d128.hip``: only the band is streamed); None or a window of
+    ``seqs.max_seqlen`` or more is plain causal attention on the causal kernels."""
+    bqkv = _varlen_check("attn_varlen_fwd", qkv, bqkv, seqs, heads, kv_heads, causal, window)
     T_, W3 = qkv.shape
+    if window is not None:
+        out = torch.empty(T_, heads * 128, dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty(heads, T_, dtype=torch.float32, device=qkv.device)
+        _lib.call("kfa_attn_window_fwd", _lib.ptr(qkv), _lib.ptr(bqkv), _lib.ptr(seqs.cu_dev), _lib.ptr(out),
+                  _lib.ptr(lse), seqs.B, T_, seqs.max_seqlen, heads, _gqa(heads, kv_heads) or heads, 128,
+                  min(int(window), 1 << 30), 1.0 / math.sqrt(128), float(p), hash_key(seed), _lib.stream())
+        return out, lse
     if _gqa(heads, kv_heads) is not None:
         out = torch.empty(T_, heads * 128, dtype=qkv.dtype, device=qkv.device)
         lse = torch.empty(heads, T_, dtype=torch.float32, device=qkv.device)
@@ -662,13 +684,14 @@ def attn_varlen_fwd(qkv, bqkv, seqs: PackedSeqs, heads, p=0.0, seed=0, causal=Fa
 
 
 def attn_varlen_bwd(qkv, bqkv, seqs: PackedSeqs, out, lse, dout, dbqkv, heads, p=0.0, seed=0, causal=False,
-                    kv_heads=None):
+                    kv_heads=None, window=None):
     """dqkv [T, 3H] of :func:`attn_varlen_fwd` (``out``, ``lse``: its outputs; unowned rows
     zero); the bias gradient is added into ``dbqkv`` (fp32 [3H], nullable).  ``causal`` as
     the forward's (attn_causal_bwd_kv_kernel / attn_causal_bwd_q_kernel).  ``kv_heads``: as the
     forward's; dqkv and ``dbqkv`` have the grouped-query width, and a KV head's gradient is the
-    sum over its group's query heads, accumulated in registers by one workgroup."""
-    bqkv = _varlen_check("attn_varlen_bwd", qkv, bqkv, seqs, heads, kv_heads)
+    sum over its group's query heads, accumulated in registers by one workgroup.  ``window``:
+    as the forward's."""
+    bqkv = _varlen_check("attn_varlen_bwd", qkv, bqkv, seqs, heads, kv_heads, causal, window)
     T_, W3 = qkv.shape
     gqa = _gqa(heads, kv_heads) is not None
     H = heads * 128 if gqa else W3 // 3
@@ -685,6 +708,12 @@ def attn_varlen_bwd(qkv, bqkv, seqs: PackedSeqs, out, lse, dout, dbqkv, heads, p
         raise ValueError("attn_varlen_bwd: dbqkv must be a contiguous fp32 [3H] vector")
     dqkv = torch.empty_like(qkv)
     work = _lib.workspace(heads * T_ * 4, qkv.device, "attn_rowdot")  # D = rowsum(dO∘O) [heads, T]
+    if window is not None:
+        _lib.call("kfa_attn_window_bwd", _lib.ptr(qkv), _lib.ptr(bqkv), _lib.ptr(seqs.cu_dev), _lib.ptr(out),
+                  _lib.ptr(lse), _lib.ptr(dout), _lib.ptr(dqkv), _lib.ptr(dbqkv), seqs.B, T_, seqs.max_seqlen, heads,
+                  kv_heads if gqa else heads, 128, min(int(window), 1 << 30), 1.0 / math.sqrt(128), float(p),
+                  hash_key(seed), _lib.ptr(work), _lib.stream())
+        return dqkv
     if gqa:
         _lib.call("kfa_attn_gqa_bwd", _lib.ptr(qkv), _lib.ptr(bqkv), _lib.ptr(seqs.cu_dev), _lib.ptr(out),
                   _lib.ptr(lse), _lib.ptr(dout), _lib.ptr(dqkv), _lib.ptr(dbqkv), seqs.B, T_, seqs.max_seqlen, heads,
@@ -698,12 +727,16 @@ def attn_varlen_bwd(qkv, bqkv, seqs: PackedSeqs, out, lse, dout, dbqkv, heads, p
 
 
 def attention_varlen_reference(qkv, bqkv, seqs: PackedSeqs, heads, keep=None, keep_scale=1.0, causal=False,
-                               kv_heads=None):
+                               kv_heads=None, window=None):
     """Plain fp32 PyTorch: ctx [T, H] of the packed batch, one sequence at a time; the
     unowned rows are zero.  ``keep`` (optional): per sequence a [heads, len, len] 0/1
     dropout keep mask, kept probabilities scaled by ``keep_scale``.  ``causal``: scores
     above each sequence's diagonal are -inf before the softmax.  ``kv_heads``: grouped-query
-    layout [T, (heads + 2·kv_heads)·d], query head h reads KV head ``h // (heads // kv_heads)``."""
+    layout [T, (heads + 2·kv_heads)·d], query head h reads KV head ``h // (heads // kv_heads)``.
+    ``window`` (with ``causal``): scores with query - key >= window are -inf as well."""
+    if window is not None and (not causal or window < 1):
+        raise ValueError(f"attention_varlen_reference: a sliding window needs causal=True and window >= 1 "
+                         f"(causal={causal}, window={window})")
     T_, W3 = qkv.shape
     kvh = heads if kv_heads is None else kv_heads
     if kvh < 1 or heads % kvh or W3 % (heads + 2 * kvh):
@@ -724,6 +757,8 @@ def attention_varlen_reference(qkv, bqkv, seqs: PackedSeqs, heads, keep=None, ke
         sc = (q @ k.transpose(-1, -2)) / math.sqrt(d)
         if causal:
             sc = sc.masked_fill(~torch.tril(torch.ones_like(sc, dtype=torch.bool)), float("-inf"))
+        if window is not None:  # query - key >= window: below the band
+            sc = sc.masked_fill(torch.tril(torch.ones_like(sc, dtype=torch.bool), -int(window)), float("-inf"))
         pr = torch.softmax(sc, -1)
         if keep is not None:
             pr = pr * keep[i] * keep_scale
@@ -796,16 +831,21 @@ class EncoderLayerFn(torch.autograd.Function):
         # sequence through the varlen kernels (B and S are not used) and key_bias is None;
         # cfg[10] (optional): causal attention (a decoder layer), packed batches only;
         # cfg[11] (optional): kv_heads of grouped-query attention (wqkv [(heads + 2·kv_heads)·d, H],
-        # d = H // heads = 128), packed batches only
+        # d = H // heads = 128), packed batches only; cfg[12] (optional): the sliding window of
+        # causal attention (query i sees its last cfg[12] keys), packed causal batches at d = 128 only
         B, S, heads, ph, pa, seed, eps = cfg[:7]
         ctx.joins = (tuple(cfg[7:9]) + (None, None))[:2]
         seqs = cfg[9] if len(cfg) > 9 else None
         causal = bool(cfg[10]) if len(cfg) > 10 else False
         kv_heads = cfg[11] if len(cfg) > 11 else None
+        window = cfg[12] if len(cfg) > 12 else None
         if causal and seqs is None:
             raise ValueError("EncoderLayerFn: causal attention needs a packed batch (cfg[9]: a PackedSeqs)")
         if kv_heads is not None and seqs is None:
             raise ValueError("EncoderLayerFn: grouped-query attention needs a packed batch (cfg[9]: a PackedSeqs)")
+        if window is not None and (seqs is None or not causal):
+            raise ValueError("EncoderLayerFn: sliding-window attention needs a packed batch (cfg[9]: a PackedSeqs) "
+                             "and causal attention (cfg[10])")
         _gemm.mark_weights_stale()  # the dgrad's cached weight transposes refresh at the next backward
         T, H = x.shape
         d = H // heads
@@ -827,7 +867,8 @@ class EncoderLayerFn(torch.autograd.Function):
         # attention
         qkv = mm(x, wqkv)                                                 # [T, 3H]
         if seqs is not None:
-            ctxr, lse = attn_varlen_fwd(qkv, bqkv, seqs, heads, pa, s_attn, causal=causal, kv_heads=kv_heads)
+            ctxr, lse = attn_varlen_fwd(qkv, bqkv, seqs, heads, pa, s_attn, causal=causal, kv_heads=kv_heads,
+                                        window=window)
             att = (qkv, lse)
         elif fused:
             ctxr, lse, amask = attn_fwd(qkv, bqkv, key_bias, B, S, heads, pa, s_attn, want_mask=True) if ATTN_MASK \
@@ -867,6 +908,7 @@ class EncoderLayerFn(torch.autograd.Function):
         ctx.seqs = seqs
         ctx.causal = causal
         ctx.kv_heads = kv_heads
+        ctx.window = window
         return h2
 
     @staticmethod
@@ -909,7 +951,7 @@ class EncoderLayerFn(torch.autograd.Function):
         if ctx.seqs is not None:
             qkv, lse = att
             dqkv = attn_varlen_bwd(qkv, bqkv, ctx.seqs, ctxr, lse, dctxr, None, heads, pa, s_attn, causal=ctx.causal,
-                                   kv_heads=ctx.kv_heads)
+                                   kv_heads=ctx.kv_heads, window=ctx.window)
             colsum_(dqkv, G(bqkv))  # as the fused path: one column-sum pass over the still-cached dqkv
             del dctxr
         elif fused:
@@ -960,15 +1002,20 @@ def encoder_layer_reference(x, key_bias, cfg, wqkv, bqkv, wo, bo, g1, be1, w1, b
     """Plain PyTorch fp32 reference (no dropout); cfg[9] (optional): the PackedSeqs of a
     packed batch (x [rows, H], attention per sequence, no key_bias); cfg[10] (optional):
     causal attention, packed batches only; cfg[11] (optional): kv_heads of grouped-query
-    attention, packed batches only."""
+    attention, packed batches only; cfg[12] (optional): the sliding window of causal attention,
+    packed causal batches only."""
     B, S, heads, _, _, _, eps = cfg[:7]
     seqs = cfg[9] if len(cfg) > 9 else None
     causal = bool(cfg[10]) if len(cfg) > 10 else False
     kv_heads = cfg[11] if len(cfg) > 11 else None
+    window = cfg[12] if len(cfg) > 12 else None
     if causal and seqs is None:
         raise ValueError("encoder_layer_reference: causal attention needs a packed batch (cfg[9])")
     if kv_heads is not None and seqs is None:
         raise ValueError("encoder_layer_reference: grouped-query attention needs a packed batch (cfg[9])")
+    if window is not None and (seqs is None or not causal):
+        raise ValueError("encoder_layer_reference: sliding-window attention needs a packed batch (cfg[9]) "
+                         "and causal attention (cfg[10])")
     T, H = x.shape
     d = H // heads
     f = lambda t: t.float()  # noqa: E731
@@ -977,7 +1024,7 @@ def encoder_layer_reference(x, key_bias, cfg, wqkv, bqkv, wo, bo, g1, be1, w1, b
     if seqs is not None:
         if key_bias is not None:
             raise ValueError("encoder_layer_reference: a packed batch takes no key_bias")
-        a = attention_varlen_reference(qkv, None, seqs, heads, causal=causal, kv_heads=kv_heads)
+        a = attention_varlen_reference(qkv, None, seqs, heads, causal=causal, kv_heads=kv_heads, window=window)
     else:
         q, k, v = qkv.view(B, S, 3, heads, d).permute(2, 0, 3, 1, 4)
         sc = (q @ k.transpose(-1, -2)) / math.sqrt(d)

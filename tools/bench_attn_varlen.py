@@ -93,6 +93,53 @@ def gqa(rounds, kv_heads):
                       f"min {min(r):.3f}, max {max(r):.3f})")
 
 
+def window(rounds, windows):
+    """--head-dim 128 --causal --window W [W ...]: sliding-window causal attention against full causal
+    attention of the same build on the same batch, 16 query heads of 128 (dropout 0.1), multi-head and
+    grouped-query with 4 KV heads: 4 sequences of 8192 tokens, 16 of 2048, and 8 with lengths uniform
+    in [1024, 8192].  Ratios are taken per round (both sides timed back to back) and printed with their
+    spread next to the ratio of visible (query, key) pairs, which is the ideal."""
+    d = torch.device("cuda")
+    g = torch.Generator().manual_seed(0)
+    torch.manual_seed(0)
+    h, hd, p, S = 16, 128, 0.1, 8192
+    H = h * hd
+    for name, lens in (("4 x 8192", torch.full((4,), 8192)), ("16 x 2048", torch.full((16,), 2048)),
+                       ("8, uniform in [1024, 8192]", torch.randint(1024, S + 1, (8,), generator=g))):
+        rows = int(lens.sum())
+        # max_seqlen is the longest sequence: a window that covers it runs the causal kernels
+        seqs = T.PackedSeqs(torch.cat([torch.zeros(1, dtype=torch.long), lens.cumsum(0)]), rows, None, d)
+        dout = torch.randn(rows, H, device=d).to(torch.bfloat16)
+        print(f"attention, {name}: {rows} rows, {h} query heads of {hd}")
+        for kvh in (h, 4):
+            qkv = torch.randn(rows, (h + 2 * kvh) * hd, device=d).to(torch.bfloat16)
+
+            def fwd(w):
+                return T.attn_varlen_fwd(qkv, None, seqs, h, p, 7, causal=True, kv_heads=kvh, window=w)
+
+            def both(w):
+                out, lse = fwd(w)
+                T.attn_varlen_bwd(qkv, None, seqs, out, lse, dout, None, h, p, 7, causal=True, kv_heads=kvh, window=w)
+
+            sides = {}
+            for w in [None] + list(windows):  # the default arguments bind this iteration's values
+                sides[(w, "fwd")] = lambda w=w: fwd(w)
+                sides[(w, "fwd+bwd")] = lambda w=w: both(w)
+            t = alternate_rounds(sides, rounds, 5)
+            print(f"  {kvh} KV heads")
+            for (w, k), v in t.items():
+                print(f"    {'causal' if w is None else 'W = %d' % w:10s} {k:8s} min {min(v):8.3f} ms  "
+                      f"median {statistics.median(v):8.3f} ms", flush=True)
+            full = float((lens * (lens + 1) / 2).sum())
+            for w in windows:
+                m = lens.clamp(max=w)
+                ideal = float((m * (m + 1) / 2 + (lens - m) * w).sum()) / full
+                for k in ("fwd", "fwd+bwd"):
+                    r = [a / b for a, b in zip(t[(w, k)], t[(None, k)])]
+                    print(f"    W = {w} {k}: window / causal = {statistics.median(r):.3f} (median of the per-round "
+                          f"ratios; min {min(r):.3f}, max {max(r):.3f}); visible pairs {ideal:.3f}")
+
+
 def head_dims(rounds):
     """--head-dim 128: one layer's attention at H = 768, dropout 0.1: 6 heads of 128
     (attention_d128.hip) against 12 heads of 64 on the SAME packed qkv (equal FLOPs), bidirectional
@@ -176,7 +223,14 @@ def main():
     ap.add_argument("--kv-heads", type=int, default=None,
                     help="with --head-dim 128: grouped-query attention with this many KV heads against the multi-head "
                          "kernels, both at 16 query heads")
+    ap.add_argument("--window", type=int, nargs="+", default=None,
+                    help="with --head-dim 128 --causal: sliding-window attention with these windows against full "
+                         "causal attention, multi-head and grouped-query, up to 8192 tokens")
     args = ap.parse_args()
+    if args.window is not None:
+        if args.head_dim != 128 or not args.causal or min(args.window) < 1:
+            ap.error("--window needs --head-dim 128 --causal and windows >= 1")
+        return window(args.rounds, args.window)
     if args.kv_heads is not None:
         if args.head_dim != 128 or args.kv_heads < 1 or 16 % args.kv_heads:
             ap.error("--kv-heads needs --head-dim 128 and a divisor of the 16 query heads")
