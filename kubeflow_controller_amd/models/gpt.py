@@ -15,6 +15,11 @@ GEMM's M is therefore the row budget, whatever the batch holds, and its route ne
 changes; the tied decoder keeps a bias (zero-initialised) as BERT's does, because the
 loss kernel produces its gradient anyway.
 
+Positions: a learned table added to the token embedding, or with ``GptConfig.rotary`` rotary
+position embeddings — no table, every layer rotates Q and K of its QKV projection by the
+token's index in its document (``csrc/kernels/rope.hip``), so a score depends on the distance
+between query and key only.
+
 Vocabulary is padded to a multiple of 64 (50257 → 50304); padded ids never occur as
 inputs or labels.
 
@@ -47,6 +52,8 @@ class GptConfig:
     init_range: float = 0.02
     kv_heads: Optional[int] = None  # grouped-query attention: K / V heads (divides heads; head dim 128 only)
     window: Optional[int] = None    # sliding-window attention: a token sees its last `window` tokens (head dim 128 only)
+    rotary: bool = False            # rotary position embeddings on Q and K instead of the learned position table
+    rotary_base: float = 10000.0
 
     @classmethod
     def small(cls) -> "GptConfig":
@@ -70,6 +77,12 @@ class GptConfig:
         """The ``xl_gqa`` shape for long documents: 8192 positions, each token attending to its
         last 1024 (sliding-window attention: attention cost is linear in the length)."""
         return cls(hidden=2048, layers=24, heads=16, kv_heads=4, intermediate=8192, max_position=8192, window=1024)
+
+    @classmethod
+    def xl_rope(cls) -> "GptConfig":
+        """The ``xl_gqa`` shape with rotary position embeddings: no learned position table, Q and K
+        rotated by in-sequence position before attention (``csrc/kernels/rope.hip``)."""
+        return cls(hidden=2048, layers=24, heads=16, kv_heads=4, intermediate=8192, max_position=2048, rotary=True)
 
     @classmethod
     def tiny(cls) -> "GptConfig":
@@ -108,10 +121,15 @@ class GptLM(nn.Module):
             if H != cfg.heads * 128:
                 raise ValueError(f"GptLM: sliding-window attention needs head dim 128, got {H / cfg.heads:g} "
                                  f"(hidden={H}, heads={cfg.heads})")
+        if cfg.rotary and (H % cfg.heads or H // cfg.heads not in (64, 128)):
+            raise ValueError(f"GptLM: rotary position embeddings need head dim 64 or 128, got {H / cfg.heads:g} "
+                             f"(hidden={H}, heads={cfg.heads})")
         self.word_emb = nn.Parameter(torch.empty(V, H))
-        self.pos_emb = nn.Parameter(torch.empty(cfg.max_position, H))
-        for w in (self.word_emb, self.pos_emb):
-            nn.init.normal_(w, 0.0, cfg.init_range)
+        nn.init.normal_(self.word_emb, 0.0, cfg.init_range)
+        if not cfg.rotary:  # learned positions; with rotary the position enters as a rotation of Q and K
+            self.pos_emb = nn.Parameter(torch.empty(cfg.max_position, H))
+            nn.init.normal_(self.pos_emb, 0.0, cfg.init_range)
+        self._rotary = {}  # device -> RotaryTable, created at the first batch on that device
         self.layers = nn.ModuleList(BertLayer(cfg) for _ in range(cfg.layers))
         self.dec_b = nn.Parameter(torch.zeros(V))
         # the word embedding is written by two direct-gradient kernels per step (lookup
@@ -126,9 +144,21 @@ class GptLM(nn.Module):
         """The packed batch carries a host sequence table that is checked before every launch."""
         return False
 
+    def rotary_table(self, device) -> Optional[T.RotaryTable]:
+        """The model's one :class:`~kubeflow_controller_amd.ops.transformer.RotaryTable` on
+        ``device`` (None without ``cfg.rotary``)."""
+        cfg = self.cfg
+        if not cfg.rotary:
+            return None
+        key = str(device)
+        if key not in self._rotary:
+            self._rotary[key] = T.RotaryTable(cfg.hidden // cfg.heads, cfg.max_position, cfg.rotary_base, device)
+        return self._rotary[key]
+
     def forward(self, input_ids, position_ids, seqs, labels):
         """Mean next-token cross-entropy over the rows that have a target.  ``input_ids``,
-        ``position_ids``, ``labels`` (:func:`next_token_labels`): flat [rows]; ``seqs``: the table."""
+        ``position_ids``, ``labels`` (:func:`next_token_labels`): flat [rows]; ``seqs``: the table.
+        With ``cfg.rotary``, ``position_ids`` is ignored: a row's position is its index in its sequence."""
         cfg = self.cfg
         if seqs.max_seqlen > cfg.max_position:
             raise ValueError(f"GptLM: max_seqlen {seqs.max_seqlen} exceeds max_position {cfg.max_position}")
@@ -141,14 +171,18 @@ class GptLM(nn.Module):
         step_seed = T.mix_seed(self.seed, self._step)
         if self.training:
             self._step += 1
-        h = T.embedding_sum([self.word_emb, self.pos_emb], [input_ids.reshape(-1), position_ids.reshape(-1)])
+        rotary = self.rotary_table(input_ids.device)
+        if rotary is None:
+            h = T.embedding_sum([self.word_emb, self.pos_emb], [input_ids.reshape(-1), position_ids.reshape(-1)])
+        else:
+            h = T.embedding_sum([self.word_emb], [input_ids.reshape(-1)])
         if ph > 0:
             h = T.dense_dropout(h, ph, T.mix_seed(step_seed, 999))
         join_in = None
         for i, layer in enumerate(self.layers):
             join_out = T.ResidualJoin() if (self.training and i + 1 < len(self.layers)) else None
             lcfg = (seqs.B, seqs.max_seqlen, cfg.heads, ph, pa, T.s64(T.mix_seed(step_seed, i)), cfg.ln_eps, join_in,
-                    join_out, seqs, True, cfg.kv_heads, cfg.window)
+                    join_out, seqs, True, cfg.kv_heads, cfg.window) + ((rotary,) if rotary is not None else ())
             h = T.EncoderLayerFn.apply(h, None, lcfg, *layer.params())
             join_in = join_out
         # decoder_xent means over all rows (ignored rows add 0): rescale to the rows with a
@@ -162,9 +196,12 @@ class GptLM(nn.Module):
         """Plain PyTorch fp32, no dropout (CPU replicas + numerics reference)."""
         cfg = self.cfg
         f = lambda t: t.float()  # noqa: E731
-        h = f(self.word_emb)[input_ids.reshape(-1)] + f(self.pos_emb)[position_ids.reshape(-1)]
+        rotary = self.rotary_table(input_ids.device)
+        h = f(self.word_emb)[input_ids.reshape(-1)]
+        if rotary is None:
+            h = h + f(self.pos_emb)[position_ids.reshape(-1)]
         lcfg = (seqs.B, seqs.max_seqlen, cfg.heads, 0.0, 0.0, 0, cfg.ln_eps, None, None, seqs, True, cfg.kv_heads,
-                cfg.window)
+                cfg.window) + ((rotary,) if rotary is not None else ())
         for layer in self.layers:
             h = T.encoder_layer_reference(h, None, lcfg, *layer.params())
         logits = h @ f(self.word_emb).t() + f(self.dec_b)

@@ -68,6 +68,7 @@ _lib.register("kfa_attn_gqa_fwd", [P, P, P, P, P, I, I, I, I, I, I, I, Fl, Fl, U
 _lib.register("kfa_attn_gqa_bwd", [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, Fl, Fl, U64, P, P])
 _lib.register("kfa_attn_window_fwd", [P, P, P, P, P, I, I, I, I, I, I, I, Fl, Fl, U64, P])
 _lib.register("kfa_attn_window_bwd", [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, Fl, Fl, U64, P, P])
+_lib.register("kfa_rope_qk", [P, P, P, P, P, I, I, I, I, I, I, I, P])
 
 # env KFA_FUSED_ATTN=0 falls back to the split kernels + batched library GEMMs
 FUSED_ATTN = os.environ.get("KFA_FUSED_ATTN", "1") != "0"
@@ -601,7 +602,26 @@ def _gqa(heads, kv_heads):
     return None if kv_heads is None or kv_heads == heads else kv_heads
 
 
-def _varlen_check(name, qkv, bqkv, seqs, heads, kv_heads=None, causal=False, window=None):
+class RotaryTable:
+    """cos / sin table of rotary position embeddings: ``table`` fp32 [max_position, head_dim/2, 2]
+    holding (cos, sin) of ``pos · base^(-2j / head_dim)``, evaluated in fp64 on the host and
+    rounded once, so neither the kernel (``csrc/kernels/rope.hip``) nor the reference calls a
+    sine.  One table serves every layer of a model."""
+
+    def __init__(self, head_dim: int, max_position: int, base: float = 10000.0, device=None):
+        if head_dim not in (64, 128):
+            raise ValueError(f"RotaryTable: head dim must be 64 or 128, got {head_dim}")
+        if max_position < 1:
+            raise ValueError(f"RotaryTable: max_position must be >= 1, got {max_position}")
+        self.head_dim, self.max_position, self.base = int(head_dim), int(max_position), float(base)
+        inv = torch.tensor(self.base, dtype=torch.float64) ** (-torch.arange(0, head_dim, 2, dtype=torch.float64) / head_dim)
+        ang = torch.arange(self.max_position, dtype=torch.float64)[:, None] * inv
+        self.table = torch.stack((ang.cos(), ang.sin()), -1).to(torch.float32).contiguous()
+        if device is not None:
+            self.table = self.table.to(device)
+
+
+def _varlen_check(name, qkv, bqkv, seqs, heads, kv_heads=None, causal=False, window=None, rotary=None):
     if not isinstance(seqs, PackedSeqs):
         raise ValueError(f"{name}: seqs must be a PackedSeqs")
     if qkv.dim() != 2 or qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
@@ -634,9 +654,20 @@ def _varlen_check(name, qkv, bqkv, seqs, heads, kv_heads=None, causal=False, win
             raise ValueError(f"{name}: sliding-window attention needs head dim 128 (qkv {tuple(qkv.shape)}, "
                              f"heads={heads}: head dim {W3 // (3 * heads)})")
     seqs.validate(T_)
+    if rotary is not None:
+        d = 128 if _gqa(heads, kv_heads) is not None else W3 // (3 * heads)
+        if not isinstance(rotary, RotaryTable):
+            raise ValueError(f"{name}: rotary must be a RotaryTable")
+        if rotary.head_dim != d:
+            raise ValueError(f"{name}: the rotary table is built for head dim {rotary.head_dim}, the heads have {d}")
+        if seqs.max_seqlen > rotary.max_position:
+            raise ValueError(f"{name}: max_seqlen {seqs.max_seqlen} exceeds the rotary table's "
+                             f"{rotary.max_position} positions")
     if not qkv.is_cuda or seqs.cu_dev.device != qkv.device:
         raise ValueError(f"{name}: qkv and the sequence table must be on the same GPU "
                          "(the CPU path is attention_varlen_reference)")
+    if rotary is not None and rotary.table.device != qkv.device:
+        raise ValueError(f"{name}: the rotary table must be on qkv's device")
     if bqkv is None:
         return _zeros_f32(W3, qkv.device)
     if bqkv.dtype != torch.float32 or bqkv.numel() != W3 or not bqkv.is_contiguous() or bqkv.device != qkv.device:
@@ -726,14 +757,56 @@ def attn_varlen_bwd(qkv, bqkv, seqs: PackedSeqs, out, lse, dout, dbqkv, heads, p
     return dqkv
 
 
+def rope_qk_(x, bias, seqs: PackedSeqs, heads, rotary: RotaryTable, kv_heads=None, inverse=False):
+    """Rotary position embeddings on the Q and K columns of ``x`` [T, 3H] (or the grouped-query
+    layout), in place (``csrc/kernels/rope.hip``: rope_qk_kernel): head by head, the rotate-half
+    pairing of ``x + bias`` by each row's position in its sequence; V columns and unowned rows are
+    untouched.  Returns the bias the attention kernel must add afterwards (fp32 [W], written by
+    the kernel: 0 on the rotated Q / K columns, ``bias`` on V).  ``inverse``: the transpose
+    rotation of a gradient (the Q / K columns of dqkv), no bias; returns None."""
+    has_bias = bias is not None and not inverse
+    _varlen_check("rope_qk_", x, bias if has_bias else None, seqs, heads, kv_heads, rotary=rotary)
+    T_, W = x.shape
+    kvh = _gqa(heads, kv_heads) or heads
+    d = W // (heads + 2 * kvh)
+    bias_out = None if inverse else torch.empty(W, dtype=torch.float32, device=x.device)
+    _lib.call("kfa_rope_qk", _lib.ptr(x), _lib.ptr(bias if has_bias else None), _lib.ptr(bias_out),
+              _lib.ptr(seqs.cu_dev), _lib.ptr(rotary.table), seqs.B, T_, seqs.max_seqlen, W, heads + kvh, d,
+              int(bool(inverse)), _lib.stream())
+    return bias_out
+
+
+def rope_reference(x, seqs: PackedSeqs, nrot, rotary: RotaryTable, inverse=False):
+    """Plain PyTorch: ``x`` [T, W] with its first ``nrot`` heads rotated by in-sequence position
+    (rotate-half pairing, the table cast to ``x``'s dtype); the other columns and the unowned
+    rows are returned as they are.  ``inverse``: the transpose rotation."""
+    d = rotary.head_dim
+    if nrot < 1 or nrot * d > x.shape[1]:
+        raise ValueError(f"rope_reference: {nrot} heads of {d} do not fit in x {tuple(x.shape)}")
+    if seqs.max_seqlen > rotary.max_position:
+        raise ValueError(f"rope_reference: max_seqlen {seqs.max_seqlen} exceeds the rotary table's "
+                         f"{rotary.max_position} positions")
+    cu = seqs.cu_host.long()
+    own = int(cu[-1])
+    pos = torch.arange(own) - torch.repeat_interleave(cu[:-1], cu[1:] - cu[:-1])
+    tab = rotary.table.to(x.device, x.dtype)[pos.to(x.device)].unsqueeze(1)      # [own, 1, d/2, 2]
+    cos, sin = tab[..., 0], (-tab[..., 1] if inverse else tab[..., 1])
+    r = x[:own, :nrot * d].reshape(own, nrot, d)
+    lo, hi = r[..., :d // 2], r[..., d // 2:]
+    rot = torch.cat((lo * cos - hi * sin, hi * cos + lo * sin), -1).reshape(own, nrot * d)
+    return torch.cat((torch.cat((rot, x[:own, nrot * d:]), 1), x[own:]))
+
+
 def attention_varlen_reference(qkv, bqkv, seqs: PackedSeqs, heads, keep=None, keep_scale=1.0, causal=False,
-                               kv_heads=None, window=None):
+                               kv_heads=None, window=None, rotary=None):
     """Plain fp32 PyTorch: ctx [T, H] of the packed batch, one sequence at a time; the
     unowned rows are zero.  ``keep`` (optional): per sequence a [heads, len, len] 0/1
     dropout keep mask, kept probabilities scaled by ``keep_scale``.  ``causal``: scores
     above each sequence's diagonal are -inf before the softmax.  ``kv_heads``: grouped-query
     layout [T, (heads + 2·kv_heads)·d], query head h reads KV head ``h // (heads // kv_heads)``.
-    ``window`` (with ``causal``): scores with query - key >= window are -inf as well."""
+    ``window`` (with ``causal``): scores with query - key >= window are -inf as well.
+    ``rotary`` (a :class:`RotaryTable`): Q and K of ``qkv + bqkv`` are rotated by in-sequence
+    position, in the input's dtype, before the scores (:func:`rope_reference`)."""
     if window is not None and (not causal or window < 1):
         raise ValueError(f"attention_varlen_reference: a sliding window needs causal=True and window >= 1 "
                          f"(causal={causal}, window={window})")
@@ -747,6 +820,12 @@ def attention_varlen_reference(qkv, bqkv, seqs: PackedSeqs, heads, keep=None, ke
     x = qkv.float()
     if bqkv is not None:
         x = x + bqkv.float()
+    if rotary is not None:
+        if not isinstance(rotary, RotaryTable) or rotary.head_dim != d:
+            raise ValueError(f"attention_varlen_reference: rotary must be a RotaryTable of head dim {d}")
+        x = rope_reference(x, seqs, heads + kvh, rotary)
+        if qkv.dtype != x.dtype:  # the rotated columns are stored in the input's dtype, as the kernel's
+            x = torch.cat((x[:, :H + kvh * d].to(qkv.dtype).to(x.dtype), x[:, H + kvh * d:]), 1)
     cu = seqs.cu_host.tolist()
     parts = []
     for i in range(len(cu) - 1):
@@ -832,15 +911,20 @@ class EncoderLayerFn(torch.autograd.Function):
         # cfg[10] (optional): causal attention (a decoder layer), packed batches only;
         # cfg[11] (optional): kv_heads of grouped-query attention (wqkv [(heads + 2·kv_heads)·d, H],
         # d = H // heads = 128), packed batches only; cfg[12] (optional): the sliding window of
-        # causal attention (query i sees its last cfg[12] keys), packed causal batches at d = 128 only
+        # causal attention (query i sees its last cfg[12] keys), packed causal batches at d = 128 only;
+        # cfg[13] (optional): the RotaryTable of rotary position embeddings — Q and K of the QKV
+        # projection are rotated in place before the attention kernel (rope_qk_), packed batches only
         B, S, heads, ph, pa, seed, eps = cfg[:7]
         ctx.joins = (tuple(cfg[7:9]) + (None, None))[:2]
         seqs = cfg[9] if len(cfg) > 9 else None
         causal = bool(cfg[10]) if len(cfg) > 10 else False
         kv_heads = cfg[11] if len(cfg) > 11 else None
         window = cfg[12] if len(cfg) > 12 else None
+        rotary = cfg[13] if len(cfg) > 13 else None
         if causal and seqs is None:
             raise ValueError("EncoderLayerFn: causal attention needs a packed batch (cfg[9]: a PackedSeqs)")
+        if rotary is not None and seqs is None:
+            raise ValueError("EncoderLayerFn: rotary position embeddings need a packed batch (cfg[9]: a PackedSeqs)")
         if kv_heads is not None and seqs is None:
             raise ValueError("EncoderLayerFn: grouped-query attention needs a packed batch (cfg[9]: a PackedSeqs)")
         if window is not None and (seqs is None or not causal):
@@ -866,7 +950,13 @@ class EncoderLayerFn(torch.autograd.Function):
                 raise ValueError(f"EncoderLayerFn: packed attention needs head dim 64 or 128, got {d}")
         # attention
         qkv = mm(x, wqkv)                                                 # [T, 3H]
-        if seqs is not None:
+        if seqs is not None and rotary is not None:
+            # qkv becomes rot(q + b) | rot(k + b) | v; bias_v: the bias left for the attention kernel (V's)
+            bias_v = rope_qk_(qkv, bqkv, seqs, heads, rotary, kv_heads)
+            ctxr, lse = attn_varlen_fwd(qkv, bias_v, seqs, heads, pa, s_attn, causal=causal, kv_heads=kv_heads,
+                                        window=window)
+            att = (qkv, lse, bias_v)
+        elif seqs is not None:
             ctxr, lse = attn_varlen_fwd(qkv, bqkv, seqs, heads, pa, s_attn, causal=causal, kv_heads=kv_heads,
                                         window=window)
             att = (qkv, lse)
@@ -909,6 +999,7 @@ class EncoderLayerFn(torch.autograd.Function):
         ctx.causal = causal
         ctx.kv_heads = kv_heads
         ctx.window = window
+        ctx.rotary = rotary
         return h2
 
     @staticmethod
@@ -949,9 +1040,11 @@ class EncoderLayerFn(torch.autograd.Function):
         res_shared = dao is dx_res  # no hidden dropout: one tensor, also the side stream's wgrad operand
         del dao
         if ctx.seqs is not None:
-            qkv, lse = att
-            dqkv = attn_varlen_bwd(qkv, bqkv, ctx.seqs, ctxr, lse, dctxr, None, heads, pa, s_attn, causal=ctx.causal,
+            qkv, lse, bias_v = att if ctx.rotary is not None else (*att, bqkv)
+            dqkv = attn_varlen_bwd(qkv, bias_v, ctx.seqs, ctxr, lse, dctxr, None, heads, pa, s_attn, causal=ctx.causal,
                                    kv_heads=ctx.kv_heads, window=ctx.window)
+            if ctx.rotary is not None:  # back to the gradient of the pre-rotation q + b, k + b
+                rope_qk_(dqkv, None, ctx.seqs, heads, ctx.rotary, ctx.kv_heads, inverse=True)
             colsum_(dqkv, G(bqkv))  # as the fused path: one column-sum pass over the still-cached dqkv
             del dctxr
         elif fused:
@@ -1003,14 +1096,18 @@ def encoder_layer_reference(x, key_bias, cfg, wqkv, bqkv, wo, bo, g1, be1, w1, b
     packed batch (x [rows, H], attention per sequence, no key_bias); cfg[10] (optional):
     causal attention, packed batches only; cfg[11] (optional): kv_heads of grouped-query
     attention, packed batches only; cfg[12] (optional): the sliding window of causal attention,
-    packed causal batches only."""
+    packed causal batches only; cfg[13] (optional): the RotaryTable of rotary position embeddings,
+    packed batches only."""
     B, S, heads, _, _, _, eps = cfg[:7]
     seqs = cfg[9] if len(cfg) > 9 else None
     causal = bool(cfg[10]) if len(cfg) > 10 else False
     kv_heads = cfg[11] if len(cfg) > 11 else None
     window = cfg[12] if len(cfg) > 12 else None
+    rotary = cfg[13] if len(cfg) > 13 else None
     if causal and seqs is None:
         raise ValueError("encoder_layer_reference: causal attention needs a packed batch (cfg[9])")
+    if rotary is not None and seqs is None:
+        raise ValueError("encoder_layer_reference: rotary position embeddings need a packed batch (cfg[9])")
     if kv_heads is not None and seqs is None:
         raise ValueError("encoder_layer_reference: grouped-query attention needs a packed batch (cfg[9])")
     if window is not None and (seqs is None or not causal):
@@ -1024,7 +1121,8 @@ def encoder_layer_reference(x, key_bias, cfg, wqkv, bqkv, wo, bo, g1, be1, w1, b
     if seqs is not None:
         if key_bias is not None:
             raise ValueError("encoder_layer_reference: a packed batch takes no key_bias")
-        a = attention_varlen_reference(qkv, None, seqs, heads, causal=causal, kv_heads=kv_heads, window=window)
+        a = attention_varlen_reference(qkv, None, seqs, heads, causal=causal, kv_heads=kv_heads, window=window,
+                                       rotary=rotary)
     else:
         q, k, v = qkv.view(B, S, 3, heads, d).permute(2, 0, 3, 1, 4)
         sc = (q @ k.transpose(-1, -2)) / math.sqrt(d)

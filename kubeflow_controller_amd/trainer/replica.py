@@ -147,10 +147,10 @@ def build(args, device):
         from ..models.bert import BertConfig, BertForPreTraining, bert_loss
         cfg = BertConfig.base() if name == "bert_base" else BertConfig.tiny()
         return BertForPreTraining(cfg), None, bert_loss
-    if name in ("gpt_small", "gpt_xl", "gpt_xl_gqa", "gpt_xl_swa", "gpt_tiny"):
+    if name in ("gpt_small", "gpt_xl", "gpt_xl_gqa", "gpt_xl_swa", "gpt_xl_rope", "gpt_tiny"):
         from ..models.gpt import GptConfig, GptLM, gpt_loss
         cfg = {"gpt_small": GptConfig.small, "gpt_xl": GptConfig.xl, "gpt_xl_gqa": GptConfig.xl_gqa,
-               "gpt_xl_swa": GptConfig.xl_swa, "gpt_tiny": GptConfig.tiny}[name]()
+               "gpt_xl_swa": GptConfig.xl_swa, "gpt_xl_rope": GptConfig.xl_rope, "gpt_tiny": GptConfig.tiny}[name]()
         return GptLM(cfg), None, gpt_loss
     if name in ("wide_deep", "wide_deep_tiny"):
         from ..models.wide_deep import WideDeep, WideDeepConfig, wide_deep_loss
@@ -643,7 +643,7 @@ def build_parser() -> argparse.ArgumentParser:
     add_cluster_flags(ap)
     ap.add_argument("--model", default="mnist_mlp",
                     help="mnist_softmax | mnist_mlp | resnet50 | resnet_tiny | bert_base | bert_tiny | "
-                         "gpt_small | gpt_xl | gpt_xl_gqa | gpt_xl_swa | gpt_tiny | wide_deep | wide_deep_tiny (the gpt models always train on "
+                         "gpt_small | gpt_xl | gpt_xl_gqa | gpt_xl_swa | gpt_xl_rope | gpt_tiny | wide_deep | wide_deep_tiny (the gpt models always train on "
                          "packed documents of [--min_seq_len, --seq_len] tokens in batch_size * seq_len rows)")
     ap.add_argument("--train_steps", type=int, default=200)
     ap.add_argument("--batch_size", type=int, default=100)

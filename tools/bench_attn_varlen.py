@@ -93,6 +93,46 @@ def gqa(rounds, kv_heads):
                       f"min {min(r):.3f}, max {max(r):.3f})")
 
 
+def rope(rounds):
+    """--rope: the two rotary passes (rope_qk_ forward on qkv with its bias, inverse on dqkv) on 32
+    sequences of 1024 tokens at 16 query / 4 KV heads of 128, each against the bytes it moves, and
+    causal grouped-query attention fwd + bwd (dropout 0.1) with and without the two passes.  A pass
+    reads and writes the (heads + kv_heads)·d rotated bf16 columns of every row once; the cos / sin
+    table (one 64-byte read per lane and row) and the bias are counted too."""
+    d = torch.device("cuda")
+    torch.manual_seed(0)
+    h, kvh, hd, p, S, B = 16, 4, 128, 0.1, 1024, 32
+    rows, W = B * S, (h + 2 * kvh) * hd
+    seqs = T.PackedSeqs(torch.arange(B + 1) * S, rows, S, d)
+    rot = T.RotaryTable(hd, S, device=d)
+    qkv = torch.randn(rows, W, device=d).to(torch.bfloat16)
+    dqkv = torch.randn(rows, W, device=d).to(torch.bfloat16)
+    dout = torch.randn(rows, h * hd, device=d).to(torch.bfloat16)
+    bqkv = torch.randn(W, device=d) * 0.01
+
+    def attn(with_rope):
+        b = T.rope_qk_(qkv, bqkv, seqs, h, rot, kvh) if with_rope else bqkv
+        out, lse = T.attn_varlen_fwd(qkv, b, seqs, h, p, 7, causal=True, kv_heads=kvh)
+        g = T.attn_varlen_bwd(qkv, b, seqs, out, lse, dout, None, h, p, 7, causal=True, kv_heads=kvh)
+        if with_rope:
+            T.rope_qk_(g, None, seqs, h, rot, kvh, inverse=True)
+
+    sides = {"rope_qk fwd": lambda: T.rope_qk_(qkv, bqkv, seqs, h, rot, kvh),
+             "rope_qk inverse": lambda: T.rope_qk_(dqkv, None, seqs, h, rot, kvh, inverse=True),
+             "attention fwd+bwd": lambda: attn(False), "attention fwd+bwd + rope": lambda: attn(True)}
+    t = alternate_rounds(sides, rounds, 20)
+    data = 2 * rows * (h + kvh) * hd * 2            # the rotated columns, read and written
+    table = rows * (hd // 2) * 2 * 4                # every row's cos / sin line
+    moved = {"rope_qk fwd": data + table + 2 * W * 4, "rope_qk inverse": data + table}
+    print(f"rotary passes, {B} x {S}: {rows} rows, {h} query / {kvh} KV heads of {hd}")
+    for k, v in t.items():
+        bw = f"  {moved[k] / 1e6:6.1f} MB moved, {moved[k] / min(v) / 1e9:5.2f} TB/s at the min" if k in moved else ""
+        print(f"  {k:26s} min {min(v) * 1e3:7.1f} us  median {statistics.median(v) * 1e3:7.1f} us{bw}", flush=True)
+    r = [a - b for a, b in zip(t["attention fwd+bwd + rope"], t["attention fwd+bwd"])]
+    print(f"  attention with the passes - without: {statistics.median(r) * 1e3:.1f} us (median of the per-round "
+          f"differences; min {min(r) * 1e3:.1f}, max {max(r) * 1e3:.1f})")
+
+
 def window(rounds, windows):
     """--head-dim 128 --causal --window W [W ...]: sliding-window causal attention against full causal
     attention of the same build on the same batch, 16 query heads of 128 (dropout 0.1), multi-head and
@@ -226,7 +266,12 @@ def main():
     ap.add_argument("--window", type=int, nargs="+", default=None,
                     help="with --head-dim 128 --causal: sliding-window attention with these windows against full "
                          "causal attention, multi-head and grouped-query, up to 8192 tokens")
+    ap.add_argument("--rope", action="store_true",
+                    help="the rotary position-embedding passes (rope_qk_ forward and inverse) at 16 query / 4 KV "
+                         "heads of 128, alone and around causal grouped-query attention")
     args = ap.parse_args()
+    if args.rope:
+        return rope(args.rounds)
     if args.window is not None:
         if args.head_dim != 128 or not args.causal or min(args.window) < 1:
             ap.error("--window needs --head-dim 128 --causal and windows >= 1")

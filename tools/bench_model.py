@@ -26,7 +26,7 @@ from kubeflow_controller_amd.trainer.engine import Engine, init_distributed, tim
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--model", default="bert_base", choices=["bert_base", "bert_large", "bert_tiny", "gpt_small",
-                                                             "gpt_xl", "gpt_xl_gqa", "gpt_xl_swa", "gpt_tiny", "wide_deep", "wide_deep_tiny"])
+                                                             "gpt_xl", "gpt_xl_gqa", "gpt_xl_swa", "gpt_xl_rope", "gpt_tiny", "wide_deep", "wide_deep_tiny"])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 64; gpt: 8, gpt_xl: 4)")
@@ -46,7 +46,7 @@ def main(argv=None) -> int:
     # gpt_xl_swa: the same budget as 1 x 8192 (its max_position)
     xl_rows = 1 if args.model == "gpt_xl_swa" else 4
     args.batch = args.batch if args.batch is not None else ((xl_rows if args.model.startswith("gpt_xl") else 8) if gpt else 64)
-    args.seq = args.seq if args.seq is not None else {"gpt_small": 1024, "gpt_xl": 2048, "gpt_xl_gqa": 2048, "gpt_xl_swa": 8192}.get(args.model, 128)
+    args.seq = args.seq if args.seq is not None else {"gpt_small": 1024, "gpt_xl": 2048, "gpt_xl_gqa": 2048, "gpt_xl_rope": 2048, "gpt_xl_swa": 8192}.get(args.model, 128)
     info = init_distributed()
     if info.device.type != "cuda":
         raise SystemExit("bench_model.py needs an MI355X")
@@ -63,7 +63,7 @@ def main(argv=None) -> int:
     elif gpt:
         from kubeflow_controller_amd.models.gpt import GptConfig, GptLM, flops_per_step, gpt_loss, synthetic_lm_batch
         cfg = {"gpt_small": GptConfig.small, "gpt_xl": GptConfig.xl, "gpt_xl_gqa": GptConfig.xl_gqa,
-               "gpt_xl_swa": GptConfig.xl_swa, "gpt_tiny": GptConfig.tiny}[args.model]()
+               "gpt_xl_swa": GptConfig.xl_swa, "gpt_xl_rope": GptConfig.xl_rope, "gpt_tiny": GptConfig.tiny}[args.model]()
         model = GptLM(cfg)
         batch = synthetic_lm_batch(cfg, args.batch * args.seq, args.seq, min(args.min_seq, args.seq), g, info.device)
         cu = batch[2].cu_host
